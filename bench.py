@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — SGFormer fwd+bwd nodes/s on an ogbn-products-shaped synthetic graph (BASELINE.json).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,21 +14,26 @@ timed region.  N > 1 shards the SAME graph by node ranges (strong scaling; sgfor
 of a (13.9 M x N)-node uniform random graph (111 M nodes at N = 8, hidden 128, 100M/run.sh recipe); every
 rank generates only its own rows (synth.synthetic_graph_shard) and no rank ever holds the global edge list.
 
+A plain run sets up, warms up, times the K steps and prints the headline line; `--dump-outputs DIR` also writes what the
+last timed step handed its caller (loss, a fixed sample of the logits, parameters / gradients / buffers after the step:
+benchlib/dump.py) as DIR/<name>.npy.  Everything else below is measured only with `--full`.
+
 Rank 0 prints ONE JSON line: the contract fields plus
-  roofline      — the dominant kernel (CSR SpMM): algorithmic bytes per launch (nnz*8 +
+  roofline.step — the whole-step HBM fraction (SURVEY.md §8d compulsory bytes / step time, arithmetic only)
+  roofline      — (--full) the dominant kernel (CSR SpMM): algorithmic bytes per launch (nnz*8 +
                   (rows+1)*8 + X read once + Y written once) / mean launch time measured with HIP events on
                   the launch stream inside the timed region, against 8 TB/s; `gather_bytes` is the no-reuse
                   traffic of the same launch (each stored entry fetching a d-wide row), the bound for a
                   uniform random graph (profiles/r02_gather_probe.md).  `traffic` = HBM bytes per launch
                   from the rocprofv3 PMC passes of THIS kernel on THIS workload (profiles/r06_spmm_pmc.json,
                   written by scripts/pmc_passes.sh; null when no pass has been recorded).
-  structured    — the same training step and the same SpMM roofline on a graph of the same size WITH
+  structured    — (--full) the same training step and the same SpMM roofline on a graph of the same size WITH
                   community structure and RANDOMLY PERMUTED node ids (synth.synthetic_graph_community): the
                   locality has to be recovered by sgf_reorder and is then exploited by the LDS-staged
                   row-block kernel.  The uniform headline graph is an expander (nothing to recover).
                   `structured.powerlaw`: three steps of the same on a power-law community graph with global hubs
                   (synth.synthetic_graph_community_powerlaw: the long-row path and skewed communities).
-  cpu_baseline  — the CPU restatement of the reference (oracle/, torch CPU kernels, all host cores) on
+  cpu_baseline  — (--full) the CPU restatement of the reference (oracle/, torch CPU kernels, all host cores) on
                   a bounded sample of the same workload, timed on this box before the GPU run.
 """
 from __future__ import annotations
@@ -53,6 +58,7 @@ if ROOT not in sys.path:
 
 from sgformer_amd import ops, synth  # noqa: E402,F401  (tests/bench_modes.py reaches ops through this module)
 from benchlib.cpu import cpu_baseline  # noqa: E402
+from benchlib.dump import write_outputs  # noqa: E402
 from benchlib.model import per_rank_memory_model, scaling_model  # noqa: E402
 from benchlib.timers import SpmmTimer, pmc_traffic, spmm_source_sha16, step_roofline  # noqa: E402,F401  (scripts/pmc_summarise.py reads the hash here)
 from benchlib.workloads import _sharded, make_inputs, run_minibatch, run_workload  # noqa: E402,F401
@@ -74,8 +80,8 @@ def parse():
                          "large/main.py:139-141 exactly as an unchanged trainer runs them under sgformer_amd.launch "
                          "(nn.NLLLoss served by the gather form, launch.patch_nll_loss); 'fused' = "
                          "sgformer_amd.loss.log_softmax_nll (same arithmetic, one pass); 'aten' = the same three lines "
-                         "on ATen's own nll_loss kernels.  The other two are timed on a few extra steps and reported "
-                         "in config.")
+                         "on ATen's own nll_loss kernels.  With --full the other two are timed on a few extra steps and "
+                         "reported in config.")
     ap.add_argument("--aten-loss", action="store_true", help="(older spelling of --loss aten)")
     ap.add_argument("--no-structured", action="store_true",
                     help="skip the second measurement on the community-structured graph with shuffled node ids")
@@ -93,6 +99,14 @@ def parse():
     ap.add_argument("--batch-size", type=int, default=100000)
     ap.add_argument("--no-minibatch-leg", action="store_true",
                     help="skip the mini-batch epoch appended to `structured` (ogbn-products, N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the `structured` legs, the "
+                         "other two loss forms, the SpMM roofline (HIP events around every SpMM launch + one single-stream "
+                         "step) and its PMC traffic; without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, a fixed seeded sample of "
+                         "the logits, parameters / gradients / buffers after the step) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB (rank 0)")
     return ap.parse_args()
 
 
@@ -149,7 +163,7 @@ def main():
         dev = torch.device("cuda", local_rank)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not DRYRUN:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not DRYRUN:
         cpu = cpu_baseline(args.workload, args.cpu_sample_nodes, args.seed)
 
     if _sharded(world):
@@ -162,8 +176,10 @@ def main():
     if args.mode == "minibatch":
         if world != 1 or DRYRUN:
             raise SystemExit("--mode minibatch is a single-GPU measurement")
-        steps, warmup = max(1, min(args.steps, 5)), max(2, min(args.warmup, 2))     # (2: every batch size captured before the clock starts)
-        r = run_minibatch(args, dev, steps, warmup)
+        steps, warmup = max(1, args.steps), 2     # (2: every batch size captured before the clock starts)
+        r = run_minibatch(args, dev, steps, warmup, instrument=args.full, keep_outputs=bool(args.dump_outputs))
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, r["outputs"])
         ms = r["elapsed"] / steps * 1e3
         line = {"metric": f"SGFormer fwd+bwd nodes/sec on {args.workload}, random-partition mini-batch epoch "
                           f"(large/main-batch.py:129-151)",
@@ -180,9 +196,12 @@ def main():
                 "cpu_baseline": cpu}
         print(json.dumps(line), flush=True)
         return
-    r = run_workload(args, args.graph, rank, world, dev, args.steps, args.warmup, with_aten=True)
+    r = run_workload(args, args.graph, rank, world, dev, args.steps, args.warmup, with_aten=args.full,
+                     instrument=args.full, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if r["outputs"] is not None:
+        write_outputs(args.dump_outputs, r["outputs"])
     structured = None
-    if (rank == 0 and world == 1 and args.graph == "uniform" and not args.no_structured
+    if (args.full and rank == 0 and world == 1 and args.graph == "uniform" and not args.no_structured
             and not args.workload.endswith("-weak") and args.workload != "cora"):
         k = max(3, min(args.steps, 5))
         q = run_workload(args, "community", rank, world, dev, k, 3)
@@ -277,7 +296,7 @@ def main():
                        "graph_view": r["view"],
                        "prepare_graph_s": None if r["prepare_s"] is None else round(r["prepare_s"], 3),
                        "exchanged": r["exchanged"],
-                       "debug_override": bool(args.nodes), **({"dry_run": True} if DRYRUN else {}),
+                       "debug_override": bool(args.nodes), "full": bool(args.full), **({"dry_run": True} if DRYRUN else {}),
                        **({"shared_gpu": "validation only: all ranks on cuda:0, gloo transport staged through the host"}
                           if SHARE_GPU else {})},
             "loss": r["loss"],

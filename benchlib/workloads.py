@@ -19,6 +19,7 @@ from sgformer_amd.loss import log_softmax_nll  # noqa: E402
 from sgformer_amd.dist import ShardContext, shard_model, sharded_nll_loss  # noqa: E402
 from sgformer_amd.ours import SGFormer  # noqa: E402
 
+from .dump import step_outputs  # noqa: E402
 from .timers import SpmmTimer, pmc_traffic  # noqa: E402
 
 def _sharded(world: int) -> bool:
@@ -57,9 +58,11 @@ def make_inputs(workload: str, nodes: int, seed: int, rank: int, world: int, dev
     return n, f, c, d, cfg, weak, ei, x, y, train_idx, n_train, ctx
 
 
-def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=False):
+def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=False, instrument=True, keep_outputs=False):
     """Build the synthetic inputs + model for one graph kind, run `warmup` untimed and `steps` timed training
-    steps (barrier + synchronize on both sides), return the measurements."""
+    steps (barrier + synchronize on both sides), return the measurements.  `instrument`: HIP events around every SpMM
+    launch of the timed steps and one more single-stream step (the SpMM roofline); `keep_outputs`: what the last timed
+    step handed its caller (benchlib.dump.step_outputs) in out["outputs"]."""
     n, f, c, d, cfg, weak, ei, x, y, train_idx, n_train, ctx = make_inputs(args.workload, args.nodes, args.seed,
                                                                            rank, world, dev, graph_kind)
     medium = args.workload == "cora"
@@ -129,6 +132,8 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
     def step():
         opt.zero_grad(set_to_none=True)
         logits = model(x, ei)
+        if state.get("keep"):
+            state["logits"] = logits
         if ctx is not None:
             loss = sharded_nll_loss(logits, y, train_idx, n_train)
         elif state["mode"] == "fused":   # the same arithmetic in one pass (sgf_nll_fwd / sgf_nll_bwd)
@@ -142,8 +147,9 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
         opt.step()
         return loss
 
-    timer = SpmmTimer()
-    timer.install()
+    timer = SpmmTimer() if instrument else None
+    if timer is not None:
+        timer.install()
     if state["mode"] == "trainer" and ctx is None:
         _launch.patch_nll_loss()
     try:
@@ -157,16 +163,23 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
             torch.cuda.synchronize()
 
         fence()
-        timer.active = True
+        if timer is not None:
+            timer.active = True
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            state["keep"] = keep_outputs and i == steps - 1
             loss = step()
         fence()
         elapsed = time.perf_counter() - t0
-        timer.active = False   # (the extra ATen-loss steps below are not part of the roofline sample)
+        if timer is not None:
+            timer.active = False   # (the extra ATen-loss steps below are not part of the roofline sample)
+        outputs = None
+        if keep_outputs:       # before any further step moves the parameters on
+            outputs = step_outputs(model, state.pop("logits"), loss)
+            state["keep"] = False
         loss_val = float(loss.detach())
         iso = None
-        if getattr(model, "overlap_branches", False) and ctx is None and not medium and timer.pairs:
+        if timer is not None and getattr(model, "overlap_branches", False) and ctx is None and not medium and timer.pairs:
             # The timed steps run the attention branch on a side stream NEXT to the SpMM launches, so the events above time
             # the SpMM sharing the chip.  One more, untimed step on ONE stream gives the kernel's own launch time as well.
             in_situ = (timer.pairs, timer.bytes_alg, timer.bytes_gather, timer.kernels)
@@ -207,8 +220,9 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
             state["mode"] = headline
     finally:
         _launch.unpatch_nll_loss()
-        timer.uninstall()
-    roof = timer.summary()
+        if timer is not None:
+            timer.uninstall()
+    roof = timer.summary() if timer is not None else None
     if roof is not None and iso is not None:
         roof["single_stream"] = {"mean_launch_ms": iso["mean_launch_ms"], "achieved": iso["achieved"], "frac": iso["frac"],
                                  "gather_GBps": iso["gather_GBps"], "launches": iso["launches"],
@@ -238,7 +252,7 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
         cfg = dict(gnn_num_layers=4, trans_num_layers=1)     # medium/run.sh:2-7 (for the whole-step byte formula)
     out = dict(n=n, f=f, c=c, d=d, weak=weak, cfg=cfg, nnz=int(ei.shape[1]), elapsed=elapsed, loss=loss_val, ms_aten=ms_aten, ms_fused=ms_fused, loss_mode=state["mode"],
                dropout=(p_trans, p_gnn),
-               roof=roof, view=view_stats, prepare_s=t_prep, exchanged=exchanged,
+               roof=roof, view=view_stats, prepare_s=t_prep, exchanged=exchanged, outputs=outputs,
                peak_mem=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
     del model, opt, x, y
     ops.graph_cache.clear()
@@ -246,14 +260,16 @@ def run_workload(args, graph_kind, rank, world, dev, steps, warmup, with_aten=Fa
     return out
 
 
-def run_minibatch(args, dev, steps, warmup):
+def run_minibatch(args, dev, steps, warmup, instrument=True, keep_outputs=False):
     """One step = one EPOCH of large/main-batch.py:129-151 as the unchanged trainer runs it under sgformer_amd.launch
     (features resident on the GPU: launch.patch_resident_features; per-batch induced subgraph on the GPU: batching.subgraph
     = torch_geometric.utils.subgraph's semantics; 16 host threads; labels and masks on the HOST as the trainer keeps them):
         idx = randperm(n);  per batch:  train_mask[idx_i], x[idx_i].to(device), subgraph(idx_i, edge_index, relabel), y[idx_i]
         .to(device), model(x_i, edge_index_i), log_softmax, criterion(out_i[train_mask_i], y_i[train_mask_i]), backward, step
     — the trainer's lines verbatim, including its boolean-mask indexing (one device->host read per batch).  The per-batch
-    breakdown comes from HIP events on the launch stream (GPU timeline, gaps included) and host timers (time to ISSUE)."""
+    breakdown comes from HIP events on the launch stream (GPU timeline, gaps included) and host timers (time to ISSUE).
+    `instrument`: the SpMM roofline (HIP events around every SpMM launch; one more, untimed epoch of eager steps when the
+    timed ones are replayed); `keep_outputs`: what the last batch of the last timed epoch handed the trainer, in out["outputs"]."""
     from sgformer_amd import batching, launch
     launch.limit_host_threads()
     n, avg_deg, f, c, d = synth.SHAPES[args.workload]
@@ -281,7 +297,9 @@ def run_minibatch(args, dev, steps, warmup):
     ev, host = [], {k: 0.0 for k in marks}
     gen_cpu = torch.Generator().manual_seed(args.seed)
 
-    def epoch(record):
+    kept = {}
+
+    def epoch(record, keep=False):
         model.train()
         idx = torch.randperm(n, generator=gen_cpu)
         for i in range(num_batch):
@@ -303,6 +321,8 @@ def run_minibatch(args, dev, steps, warmup):
                 e[2].record()
             opt.zero_grad()
             out_i = model(x_i, ei_i)
+            if keep and i == num_batch - 1:
+                kept["logits"] = out_i
             t.append(time.perf_counter())
             if record:
                 e[3].record()
@@ -322,23 +342,27 @@ def run_minibatch(args, dev, steps, warmup):
         return loss
 
     launch.patch_nll_loss()
-    timer = SpmmTimer()
-    timer.install()
+    timer = SpmmTimer() if instrument else None
+    if timer is not None:
+        timer.install()
     try:
         for _ in range(warmup):
             epoch(False)
         torch.cuda.synchronize()
         from sgformer_amd import graphed
         replayed, replays0 = graphed.enabled(), graphed.counters["replays"]
-        timer.active = not replayed
+        if timer is not None:
+            timer.active = not replayed
         t0 = time.perf_counter()
-        for _ in range(steps):
-            loss = epoch(True)
+        for j in range(steps):
+            loss = epoch(True, keep_outputs and j == steps - 1)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        timer.active = False
+        outputs = step_outputs(model, kept.pop("logits"), loss) if keep_outputs else None
+        if timer is not None:
+            timer.active = False
         replays = graphed.counters["replays"] - replays0          # (0: enabled, but no batch was eligible / the capture failed)
-        if replayed:
+        if replayed and timer is not None:
             # the timed epochs replay captured steps (sgformer_amd/graphed.py): no per-launch events in there.  The SpMM
             # launches are timed in one more, UNTIMED epoch of eager steps — the same kernels on the same batches' sizes.
             keep, n_ev = os.environ.get("SGF_BATCH_GRAPH"), len(ev)
@@ -356,7 +380,8 @@ def run_minibatch(args, dev, steps, warmup):
             del ev[n_ev:]
     finally:
         launch.unpatch_nll_loss()
-        timer.uninstall()
+        if timer is not None:
+            timer.uninstall()
     gpu = {k: 0.0 for k in marks}
     for e in ev:
         for k, a, b in zip(marks, e, e[1:]):
@@ -367,8 +392,9 @@ def run_minibatch(args, dev, steps, warmup):
                  "per_batch_ms_on_the_gpu_timeline": {k: round(v / nb, 3) for k, v in gpu.items()},
                  "per_batch_ms_host_issue": {k: round(v / nb * 1e3, 3) for k, v in host.items()},
                  "per_batch_ms_wall": round(elapsed / nb * 1e3, 3)}
-    out = dict(n=n, f=f, c=c, d=d, nnz=int(ei.shape[1]), elapsed=elapsed, loss=float(loss.detach()), roof=timer.summary(),
-               breakdown=breakdown, peak_mem=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+    out = dict(n=n, f=f, c=c, d=d, nnz=int(ei.shape[1]), elapsed=elapsed, loss=float(loss.detach()),
+               roof=timer.summary() if timer is not None else None, breakdown=breakdown, outputs=outputs,
+               peak_mem=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
     del model, opt, x
     ops.graph_cache.clear()
     torch.cuda.empty_cache()

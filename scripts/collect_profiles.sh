@@ -9,7 +9,7 @@ O=gpurun_out/${ROUND:-r4}_profiles
 cd $R && mkdir -p $O
 for g in uniform community; do
   timeout 500 rocprofv3 --kernel-trace --stats -d $O/bench_$g -o b --output-format csv -- \
-    python bench.py --graph $g --steps 5 --warmup 2 --no-cpu-baseline --no-structured > $O/bench_$g.log 2>&1
+    python bench.py --full --graph $g --steps 5 --warmup 2 --no-cpu-baseline --no-structured > $O/bench_$g.log 2>&1
 done
 if [ -z "$SKIP_PMC" ]; then   # SKIP_PMC=1: the SpMM sources did not change since the last passes (bench.py checks the hash)
 bash scripts/pmc_passes.sh $O/pmc_community python scripts/spmm_pmc_target.py --graph community
@@ -25,7 +25,7 @@ for grp in "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_
            "SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   i=$((i+1))
   timeout 400 rocprofv3 --pmc $grp -d $O/mfma$i -o m --output-format csv -- \
-    python bench.py --graph uniform --steps 2 --warmup 1 --no-cpu-baseline --no-structured > $O/mfma$i.log 2>&1
+    python bench.py --full --graph uniform --steps 2 --warmup 1 --no-cpu-baseline --no-structured > $O/mfma$i.log 2>&1
 done
 find $O -name "*.csv" -size +20M -delete     # keep the artefact set small (per-dispatch counter dumps of bench are large)
 du -sh $O

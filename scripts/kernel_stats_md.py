@@ -3,7 +3,7 @@
 
     python scripts/kernel_stats_md.py <trace dir> <bench log> <out.md> <steps in trace> "<command line>"
 
-`steps in trace`: bench.py --steps 5 --warmup 2 runs 2 + 5 steps, then 1 + 5 with each of the two other loss forms = 19
+`steps in trace`: bench.py --full --steps 5 --warmup 2 runs 2 + 5 steps, then 1 + 5 with each of the two other loss forms = 19
 (--mode minibatch: epochs x batches)."""
 import csv
 import glob

@@ -19,7 +19,7 @@ from collections import defaultdict
 import pandas as pd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STEPS_IN_TRACE = 19     # bench.py --steps 5 --warmup 2: 2 + 5, then 1 + 5 with the ATen loss lines, then 1 + 5 with them under the launcher
+STEPS_IN_TRACE = 19     # bench.py --full --steps 5 --warmup 2: 2 + 5, then 1 + 5 with the ATen loss lines, then 1 + 5 with them under the launcher
 
 
 def short(name):
@@ -39,7 +39,7 @@ def kernel_stats(src_dir, log, graph, out_base):
                          "ms_per_step": round(float(r["TotalDurationNs"]) / 1e6 / STEPS_IN_TRACE, 3),
                          "Percentage": round(100 * float(r["TotalDurationNs"]) / total, 4)} for r in rows[:48]])
     with open(out_base + ".md", "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats of `python bench.py --graph {graph} --steps 5 --warmup 2 "
+        f.write(f"# rocprofv3 --kernel-trace --stats of `python bench.py --full --graph {graph} --steps 5 --warmup 2 "
                 f"--no-cpu-baseline --no-structured` (MI355X, bf16)\n\n")
         f.write(f"{STEPS_IN_TRACE} training steps are in the trace (2 warm-up + 5 timed, 1 + 5 with the trainer's ATen loss ops, 1 + 5 with the same lines and the launcher's nll_loss) "
                 "plus the one-off graph preparation\n(CSR build, `sgf_reorder`, `sgf_spmm_plan`: the rocPRIM / k_vote_* / "
@@ -81,7 +81,7 @@ def counters(src, tag):
         f.write(f"# {tag} — MFMA-busy / SQ counters of the matrix-core kernels in one training step (MI355X, bf16, "
                 "ogbn-products shape)\n\n")
         f.write("`rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F32 "
-                "SQ_VALU_MFMA_BUSY_CYCLES -- python bench.py --steps 2 --warmup 1 ...`\nand a second pass with "
+                "SQ_VALU_MFMA_BUSY_CYCLES -- python bench.py --full --steps 2 --warmup 1 ...`\nand a second pass with "
                 "`SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY` "
                 "(scripts/collect_profiles.sh, summarised by scripts/profiles_summarise.py); means per dispatch.\n"
                 "`mfma_busy_frac` = SQ_VALU_MFMA_BUSY_CYCLES / (SQ_BUSY_CYCLES / 32 shader engines x 1024 SIMDs): the share "

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r5_last; mkdir -p $O
 t0=$(date +%s)
-timeout 800 python bench.py > $O/bench_default2.json 2> $O/bench_default2.err
+timeout 800 python bench.py --full > $O/bench_default2.json 2> $O/bench_default2.err
 echo "bench.py wall: $(( $(date +%s) - t0 )) s"
 python - <<'PY'
 import json

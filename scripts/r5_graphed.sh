@@ -5,9 +5,9 @@ O=gpurun_out/r5g; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_graphed.py tests/test_gpu_r05.py tests/test_gpu_gemm.py tests/test_gpu_surface.py -x -q -m gpu > $O/tests.log 2>&1; echo "tests rc=$?" >> $O/tests.log
 tail -4 $O/tests.log
 for i in 1 2; do
-timeout 300 python bench.py --mode minibatch --steps 4 --warmup 1 $([ $i = 2 ] && echo --no-cpu-baseline) > $O/mb_graph$i.json 2> $O/mb_graph$i.err
+timeout 300 python bench.py --full --mode minibatch --steps 4 --warmup 1 $([ $i = 2 ] && echo --no-cpu-baseline) > $O/mb_graph$i.json 2> $O/mb_graph$i.err
 done
-SGF_BATCH_GRAPH=0 timeout 300 python bench.py --mode minibatch --steps 4 --warmup 1 --no-cpu-baseline > $O/mb_eager.json 2> $O/mb_eager.err
+SGF_BATCH_GRAPH=0 timeout 300 python bench.py --full --mode minibatch --steps 4 --warmup 1 --no-cpu-baseline > $O/mb_eager.json 2> $O/mb_eager.err
 timeout 200 python scripts/minibatch_sections.py --batches 12 > $O/sections_graph.json 2> $O/sections_graph.err
 python - <<'PY'
 import json

@@ -6,8 +6,8 @@ cd $R && mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_gramx.py -x -q -k "gramb2 or head_backward" 2>&1 | tail -6 > $O/gramx.txt
 timeout 900 python -m pytest tests/test_gpu_graphed.py tests/test_gpu_launch_patches.py tests/test_gpu_golden.py tests/test_gpu_model.py -x -q 2>&1 | tail -8 > $O/tests.txt
 for v in 0 1; do
-  SGF_OVERLAP=$v timeout 200 python bench.py --no-structured --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_overlap$v.json 2> $O/bench_overlap$v.err
-  SGF_OVERLAP=$v timeout 200 python bench.py --graph community --no-structured --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_comm_overlap$v.json 2> $O/bench_comm_overlap$v.err
+  SGF_OVERLAP=$v timeout 200 python bench.py --full --no-structured --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_overlap$v.json 2> $O/bench_overlap$v.err
+  SGF_OVERLAP=$v timeout 200 python bench.py --full --graph community --no-structured --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_comm_overlap$v.json 2> $O/bench_comm_overlap$v.err
 done
 SGF_OVERLAP=1 timeout 1200 python -m pytest tests/test_gpu_model.py tests/test_gpu_golden.py tests/test_gpu_blocked.py tests/test_gpu_scale.py -x -q 2>&1 | tail -6 > $O/tests_overlap.txt
 cat $O/gramx.txt $O/tests.txt $O/tests_overlap.txt

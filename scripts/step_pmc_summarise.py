@@ -32,7 +32,7 @@ def main(src, stats_csv):
     fetch, write = counter(src, "FETCH_SIZE"), counter(src, "WRITE_SIZE")
     dur = {short(r["Name"]): (float(r["AverageNs"]) / 1e3, int(r["Calls"])) for r in csv.DictReader(open(stats_csv))}
     print("# HBM traffic per launch of the kernels of one training step (MI355X, bf16, ogbn-products shape, one stream)\n")
-    print("`rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` in separate passes over `SGF_OVERLAP=0 python bench.py --graph "
+    print("`rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` in separate passes over `SGF_OVERLAP=0 python bench.py --full --graph "
           "uniform --steps 2 --warmup 1 --no-cpu-baseline --no-structured` (scripts/r6_final.sh); HBM bytes = 2 x FETCH_SIZE KiB + "
           "WRITE_SIZE KiB; `avg us` from the kernel-trace statistics of the same command with 5 timed steps.  T = N d s = 1.254 GB.\n")
     print("| kernel | launches in the pass | HBM read GB | HBM write GB | total GB | in T | avg us | TB/s on measured bytes |")

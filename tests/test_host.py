@@ -330,22 +330,20 @@ def test_medium_module_matches_oracle(cpu_table, cfg, gcn_layers):
 
 def test_medium_state_dict_matches_reference_keys():
     """Same parameter names / shapes as medium/ours.py + models.GCN over PyG 1.7.2 GCNConv
-    (`gnn.convs.i.weight [in, out]`, `gnn.convs.i.bias`, `gnn.bns.i.*`): checkpoints interchange."""
-    from oracle import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip("/root/reference not mounted")
+    (`gnn.convs.i.weight [in, out]`, `gnn.convs.i.bias`, `gnn.bns.i.*`): checkpoints interchange.  The reference's
+    state_dict is the stored one (tests/golden/live, oracle/live_golden.py) and a fresh one when the reference is mounted."""
+    from oracle import live_golden as LG
     from sgformer_amd import ours_medium as M
-    ref = ref_shim.load_reference("medium")
-    torch.manual_seed(0)
-    a = ref.SGFormer(30, 16, 4, num_layers=1, gnn=ref.models.GCN(30, 16, 16, num_layers=4))
-    torch.manual_seed(0)
-    b = M.SGFormer(30, 16, 4, num_layers=1, gnn=M.GCN(30, 16, 16, num_layers=4))
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa.keys()) == list(sb.keys())
-    for k in sa:
-        assert sa[k].shape == sb[k].shape, k
-        assert torch.equal(sa[k], sb[k]), k          # same creation order -> same seeded init
-    b.load_state_dict(sa)
+    for rec in LG.records("state_dict_medium", LG.record_state_dict, "medium"):
+        sa = rec["state"]
+        torch.manual_seed(0)
+        b = M.SGFormer(30, 16, 4, num_layers=1, gnn=M.GCN(30, 16, 16, num_layers=4))
+        sb = b.state_dict()
+        assert list(sa.keys()) == list(sb.keys())
+        for k in sa:
+            assert sa[k].shape == sb[k].shape, k
+            assert torch.equal(sa[k], sb[k]), k          # same creation order -> same seeded init
+        b.load_state_dict(sa)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -474,19 +472,15 @@ def test_difformer_module_matches_oracle(cpu_table, cfg):
 
 
 def test_difformer_state_dict_matches_reference_keys():
-    from oracle import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip("/root/reference not mounted")
+    from oracle import live_golden as LG
     from sgformer_amd import difformer as M
-    ref = ref_shim.load_reference("difformer")
-    torch.manual_seed(0)
-    a = ref.DIFFormer(30, 16, 4, num_layers=2, num_heads=2)
-    torch.manual_seed(0)
-    b = M.DIFFormer(30, 16, 4, num_layers=2, num_heads=2)
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa.keys()) == list(sb.keys())
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
+    for rec in LG.records("state_dict_difformer", LG.record_state_dict, "difformer"):
+        sa = rec["state"]
+        torch.manual_seed(0)
+        sb = M.DIFFormer(30, 16, 4, num_layers=2, num_heads=2).state_dict()
+        assert list(sa.keys()) == list(sb.keys())
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), k
 
 
 def test_kernel_probe_drives_the_kernel_table(cpu_table):

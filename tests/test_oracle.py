@@ -1,6 +1,7 @@
 """Pins for the oracle (CPU, no GPU): oracle/sgformer_oracle.py against
   (a) the committed golden vectors dumped from the LIVE reference by oracle/make_golden.py,
-  (b) the live reference itself when /root/reference is mounted (build container only).
+  (b) the live reference's outputs on the tests' own inputs (tests/golden/live, oracle/live_golden.py), and the
+      reference itself as well when it is mounted (build container only).
 Everything is float64: agreement is to rounding (1e-12), not to a model tolerance.
 """
 import glob
@@ -11,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_shim, sgformer_oracle as O
+from oracle import live_golden as LG, sgformer_oracle as O
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
 
@@ -121,96 +122,50 @@ def test_oracle_matches_golden(path):
         assert np.array_equal(val.view(np.uint32), z["coo/value"].view(np.uint32))
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not mounted")
-@pytest.mark.parametrize("cfg", [
-    dict(trans_num_layers=1, gnn_num_layers=2, gnn_use_init=True, graph_weight=0.5, trans_use_act=False),
-    dict(trans_num_layers=2, trans_num_heads=2, gnn_num_layers=1, aggregate="cat"),
-    dict(trans_use_weight=False, trans_num_heads=2, gnn_use_weight=False, gnn_use_bn=False, trans_use_bn=False),
-    dict(use_graph=False),
-])
+@pytest.mark.parametrize("cfg", LG.LARGE_CFGS)
 def test_oracle_matches_live_reference(cfg):
-    ref = ref_shim.load_reference("large")
+    """large/ours.py executed unchanged: its stored outputs (tests/golden/live, oracle/live_golden.py), and a fresh run of it
+    when the reference is mounted."""
+    name = f"large_cfg{LG.LARGE_CFGS.index(cfg)}"
     torch.set_default_dtype(torch.float64)
     try:
-        torch.manual_seed(3)
-        n, f, d, c = 211, 18, 16, 5
-        m = ref.SGFormer(f, d, c, trans_dropout=0.0, gnn_dropout=0.0, **cfg).double()
-        x = torch.randn(n, f)
-        ei = O.synthetic_graph(n, 6.0, seed=8)
-        p = {k: v.detach().clone() for k, v in m.state_dict().items()}
-        m.train()
-        a = m(x, ei)
-        b = O.sgformer_forward(p, x, ei, cfg, training=True)
-        assert float((a - b).abs().max()) <= 1e-12
-        m.eval()
-        p = {k: v.detach().clone() for k, v in m.state_dict().items()}
-        assert float((m(x, ei) - O.sgformer_forward(p, x, ei, cfg, training=False)).abs().max()) <= 1e-12
+        for rec in LG.records(name, LG.record_large, cfg):
+            x, ei = rec["x"], rec["edge_index"]
+            b = O.sgformer_forward(rec["state/train"], x, ei, cfg, training=True)
+            assert float((rec["out/train"] - b).abs().max()) <= 1e-12
+            e = O.sgformer_forward(rec["state/eval"], x, ei, cfg, training=False)
+            assert float((rec["out/eval"] - e).abs().max()) <= 1e-12
     finally:
         torch.set_default_dtype(torch.float32)
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not mounted")
-@pytest.mark.parametrize("cfg,gcn_layers", [(dict(num_layers=1, alpha=0.5, graph_weight=0.8), 4),
-                                            (dict(num_layers=2, num_heads=2, use_weight=False, aggregate="cat"), 2),
-                                            (dict(num_layers=1, use_bn=False, use_residual=False), 3)])
+@pytest.mark.parametrize("cfg,gcn_layers", LG.MEDIUM_CASES)
 def test_medium_oracle_matches_live_reference(cfg, gcn_layers):
     """medium/ours.py and medium/models.py executed unchanged (GCNConv = the restatement in
-    oracle/ref_shim.py: torch_geometric is not installed, SURVEY.md App. D vii)."""
-    ref = ref_shim.load_reference("medium")
+    oracle/ref_shim.py: torch_geometric is not installed, SURVEY.md App. D vii): stored outputs, and a fresh run when the
+    reference is mounted."""
+    name = f"medium_cfg{LG.MEDIUM_CASES.index((cfg, gcn_layers))}"
     torch.set_default_dtype(torch.float64)
     try:
-        torch.manual_seed(5)
-        n, f, d, c = 160, 22, 16, 6
-        gnn = ref.models.GCN(f, d, d, num_layers=gcn_layers, dropout=0.0)
-        m = ref.SGFormer(f, d, c, dropout=0.0, gnn=gnn, **cfg).double()
-        with torch.no_grad():
-            for k, v in m.state_dict().items():
-                if k.endswith("bias"):
-                    v.normal_(0, 0.1)
-
-        class Data:
-            pass
-        data = Data()
-        x = torch.randn(n, f)
-        ei = O.synthetic_graph(n, 5.0, seed=9)[:, :-n]
-        data.graph = {"node_feat": x, "edge_index": ei}
-        for training in (True, False):
-            m.train(training)
-            p = {k: v.detach().clone() for k, v in m.state_dict().items()}
-            with torch.no_grad():
-                a = m(data)
-            assert float((a - O.medium_forward(p, x, ei, cfg, training=training)).abs().max()) <= 1e-12
+        for rec in LG.records(name, LG.record_medium, cfg, gcn_layers):
+            x, ei = rec["x"], rec["edge_index"]
+            for mode, training in (("train", True), ("eval", False)):
+                b = O.medium_forward(rec[f"state/{mode}"], x, ei, cfg, training=training)
+                assert float((rec[f"out/{mode}"] - b).abs().max()) <= 1e-12
     finally:
         torch.set_default_dtype(torch.float32)
 
 
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not mounted")
-@pytest.mark.parametrize("cfg", [dict(num_layers=2, num_heads=1),
-                                 dict(num_layers=1, num_heads=2, use_weight=False, graph_weight=0.3, use_source=True),
-                                 dict(num_layers=2, num_heads=2, use_graph=False, use_bn=False, use_residual=False)])
+@pytest.mark.parametrize("cfg", LG.DIFFORMER_CFGS)
 def test_difformer_oracle_matches_live_reference(cfg):
-    """medium/difformer.py executed unchanged (kernel='simple') against oracle.difformer_forward."""
-    ref = ref_shim.load_reference("difformer")
+    """medium/difformer.py executed unchanged (kernel='simple') against oracle.difformer_forward: stored outputs, and a
+    fresh run when the reference is mounted."""
+    name = f"difformer_cfg{LG.DIFFORMER_CFGS.index(cfg)}"
     torch.set_default_dtype(torch.float64)
     try:
-        torch.manual_seed(0)
-        n, f, d, c = 150, 20, 16, 5
-        m = ref.DIFFormer(f, d, c, dropout=0.0, **cfg).double()
-        with torch.no_grad():
-            for k, v in m.state_dict().items():
-                if k.endswith("bias"):
-                    v.normal_(0, 0.1)
-
-        class Data:
-            pass
-        data = Data()
-        x = torch.randn(n, f)
-        ei = O.synthetic_graph(n, 5.0, seed=3)
-        data.graph = {"node_feat": x, "edge_index": ei}
-        m.train()
-        p = {k: v.detach().clone() for k, v in m.state_dict().items()}
-        with torch.no_grad():
-            assert float((m(data) - O.difformer_forward(p, x, ei, cfg)).abs().max()) <= 1e-12
+        for rec in LG.records(name, LG.record_difformer, cfg):
+            b = O.difformer_forward(rec["state/train"], rec["x"], rec["edge_index"], cfg)
+            assert float((rec["out/train"] - b).abs().max()) <= 1e-12
     finally:
         torch.set_default_dtype(torch.float32)
 
