@@ -18,7 +18,8 @@
  *   - return value: 0 = ok, negative = error (SGF_E_*); sgf_last_error() gives the text of the
  *     most recent failure ON THE CALLING THREAD (errno-style; valid until that thread's next failure).
  *   - matrices are row-major with an explicit leading dimension `ld*` counted in ELEMENTS.
- *   - dtype codes: SGF_F32 = 0 (fp32 storage), SGF_BF16 = 1 (bf16 storage, fp32 accumulate).
+ *   - dtype codes: SGF_F32 = 0 (fp32 storage), SGF_BF16 = 1 (bf16 storage, fp32 accumulate),
+ *     SGF_F32_BF16X3 = 2 (fp32 storage whose matrix products are formed as three bf16 products, see below).
  */
 #ifndef SGF_H_
 #define SGF_H_
@@ -30,10 +31,18 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 600 /* 0.6.0: sgf_gram2_bn_bwd; the node reductions (sgf_gram, sgf_gram2, sgf_gram_bn_bwd, sgf_gram_ln_bwd, sgf_attn_h_bwd_reduce_scaled) stream their tiles by LDS-DMA (csrc/gramx.hip) */
+#define SGF_VERSION 610 /* 0.6.1: dtype code SGF_F32_BF16X3, accepted by the fp32 Linear entries (sgf_gcn_epilogue_stats, _dx, _dx2, _partial, _stats_add, sgf_combine_fc_fwd / _bwd) and by sgf_gram / sgf_gram2 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
+/* SGF_F32_BF16X3: fp32 storage (every tensor exactly as for SGF_F32) whose matrix products are formed as three bf16
+ * products, a = hi + lo with hi = bf16(a), lo = bf16(a - hi) (round to nearest even; lo = 0 where hi is not finite):
+ *     a b ~ hi_a hi_b + hi_a lo_b + lo_a hi_b,  fp32 accumulation,
+ * torch.set_float32_matmul_precision('high') ("each float32 number as the sum of two bfloat16 numbers").  Per product the
+ * error is at most 3 * 2^-16 |a b|; an inf / NaN input gives a non-finite output wherever SGF_F32 would.  Accepted only
+ * by the entries that say so and by their *_supported queries (same shapes as SGF_F32); every other entry rejects it.
+ * Where `dtype` names an output's storage (sgf_combine_fc_bwd: dx1 / dx2), SGF_F32_BF16X3 means fp32 outputs. */
+#define SGF_F32_BF16X3 2
 
 #define SGF_OK 0
 #define SGF_E_INVALID (-1)   /* bad argument (shape, alignment, dtype)            */

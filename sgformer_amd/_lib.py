@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsgf.so")
 
 SGF_F32 = 0
 SGF_BF16 = 1
+SGF_F32_BF16X3 = 2   # fp32 storage, matrix products as three bf16 products (include/sgf.h)
 
 _lib = None
 

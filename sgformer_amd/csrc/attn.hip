@@ -1353,7 +1353,7 @@ using namespace sgf;
 namespace {
 template <typename T>
 int gram_t(const void* a, int64_t lda, int m, const void* b, int64_t ldb, int k, int64_t n, float* c,
-           int64_t ldc, float* colsum_a, void* ws, hipStream_t st) {
+           int64_t ldc, float* colsum_a, void* ws, hipStream_t st, bool x3 = false) {
   SGF_REQUIRE(aligned4<T>(a, lda) && aligned4<T>(b, ldb), SGF_E_INVALID,
               "sgf_gram: a / b must be 4-element aligned with ld %% 4 == 0");
   for (int mi = 0; mi < m; mi += 256) {
@@ -1362,9 +1362,12 @@ int gram_t(const void* a, int64_t lda, int m, const void* b, int64_t ldb, int k,
       const int kb = k - ki < 256 ? k - ki : 256;
       const T* ap = static_cast<const T*>(a) + mi;
       const T* bp = static_cast<const T*>(b) + ki;
-      if (sizeof(T) == 2 && gramx_supported(ap, lda, mb, bp, ldb, kb, n)) {   // tiles by LDS-DMA (csrc/gramx.hip)
+      const bool f32x = sizeof(T) == 4 && x3;       // SGF_F32_BF16X3: three bf16 products (csrc/gram_f32x.hip)
+      if (f32x || (sizeof(T) == 2 && gramx_supported(ap, lda, mb, bp, ldb, kb, n))) {   // gramx: tiles by LDS-DMA
         int nblk = 0;
-        int rc = gramx_gram(ap, lda, mb, bp, ldb, nullptr, 0, kb, n, static_cast<float*>(ws), &nblk, st);
+        int rc = f32x ? gram_f32x(reinterpret_cast<const float*>(ap), lda, mb, reinterpret_cast<const float*>(bp), ldb, kb, n,
+                                  static_cast<float*>(ws), &nblk, st)
+                      : gramx_gram(ap, lda, mb, bp, ldb, nullptr, 0, kb, n, static_cast<float*>(ws), &nblk, st);
         if (rc != SGF_OK) return rc;
         const int64_t len = static_cast<int64_t>(mb) * kb + mb;
         float* cs = (colsum_a != nullptr && ki == 0) ? colsum_a + mi : nullptr;
@@ -1527,7 +1530,7 @@ extern "C" int sgf_gram2(const void* a, int64_t lda, int32_t m, const void* b1, 
   const char* fn = "sgf_gram2";
   SGF_REQUIRE(n >= 0 && m >= 1 && k >= 1, SGF_E_INVALID, "%s: bad sizes n=%lld m=%d k=%d", fn, static_cast<long long>(n), m, k);
   SGF_REQUIRE(m % 4 == 0 && k % 4 == 0, SGF_E_UNSUPPORTED, "%s: m and k must be multiples of 4 (m=%d k=%d)", fn, m, k);
-  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
+  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16 || dtype == SGF_F32_BF16X3, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
   SGF_REQUIRE(c1 && c2 && ldc1 >= k && ldc2 >= k, SGF_E_INVALID, "%s: null c or ldc < k", fn);
   const int R = dtype == SGF_BF16 && m <= 256 && k <= 256
                     ? reduce_rows_per_tile<uint16_t, kModeGram>(padded_dim(m > k ? m : k)) : 1;
@@ -1622,7 +1625,8 @@ extern "C" int sgf_gram(const void* a, int64_t lda, int32_t m, const void* b, in
               static_cast<long long>(n), m, k);
   SGF_REQUIRE(m % 4 == 0 && k % 4 == 0, SGF_E_UNSUPPORTED,
               "sgf_gram: m and k must be multiples of 4 (m=%d k=%d)", m, k);
-  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "sgf_gram: unknown dtype %d", dtype);
+  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16 || dtype == SGF_F32_BF16X3, SGF_E_INVALID, "sgf_gram: unknown dtype %d",
+              dtype);
   SGF_REQUIRE(c && ldc >= k, SGF_E_INVALID, "sgf_gram: null c or ldc < k");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
@@ -1633,7 +1637,8 @@ extern "C" int sgf_gram(const void* a, int64_t lda, int32_t m, const void* b, in
   SGF_REQUIRE(a && b, SGF_E_INVALID, "sgf_gram: null operand");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_gram_workspace_bytes(n, m, k), SGF_E_WORKSPACE,
               "sgf_gram: workspace too small");
-  if (dtype == SGF_F32) return gram_t<float>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st);
+  if (dtype == SGF_F32 || dtype == SGF_F32_BF16X3)
+    return gram_t<float>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st, dtype == SGF_F32_BF16X3);
   return gram_t<uint16_t>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st);
 }
 

@@ -188,15 +188,32 @@ int hrow_bwd(const void* h, int64_t ldh, const void* g, int64_t ldg, const void*
              int64_t n, int d, const float* M, const float* w, const float* Dm, const float* ds, void* dh, int64_t lddh,
              void* partial, hipStream_t st);
 
+// fp32 storage, whichever way its matrix products are formed (SGF_F32: exact; SGF_F32_BF16X3: three bf16 products)
+inline bool f32_storage(int dtype) { return dtype == SGF_F32 || dtype == SGF_F32_BF16X3; }
+
+// ---- SGF_F32_BF16X3: an fp32 value as the sum of two bf16 values (csrc/linear_f32x.hip, csrc/gram_f32x.hip) -------------
+// hi = bf16_rne(a), lo = bf16_rne(a - hi) (the subtraction is exact in fp32); lo = 0 where hi is not finite, so that an
+// inf / NaN reaches the products through hi alone (a - inf would be NaN).  Two values in, packed pairs out (element 0 low).
+__device__ __forceinline__ void split_bf16x2(float a0, float a1, uint32_t& hi, uint32_t& lo) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  const f32x2_t v = {a0, a1};
+  hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));   // v_cvt_pk_bf16_f32: round to nearest even
+  const float h0 = __uint_as_float(hi << 16), h1 = __uint_as_float(hi & 0xffff0000u);
+  const f32x2_t r = {__builtin_isfinite(h0) ? a0 - h0 : 0.f, __builtin_isfinite(h1) ? a1 - h1 : 0.f};
+  lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2_t));
+}
+
 // ---- fp32-storage Linear layers on the exact-fp32 matrix cores (csrc/linear_f32.hip), used by csrc/rowgemm.hip ----
+// (x3 != 0: the same product as three bf16 matrix-core products, SGF_F32_BF16X3, csrc/linear_f32x.hip; fp32 rows only)
 bool linear_f32_supported(int d_in, int d_out);
 int linear_f32_blocks(int64_t n);
 int linear_f32(const float* a, int64_t lda, int64_t n, int dk, int dj, const float* w, int64_t ldw, int trans_w,
                const float* bias, const float* addend, int64_t ldadd, const float* shift, float* out, int64_t ldo,
-               float* spart, hipStream_t st);
+               float* spart, hipStream_t st, int x3 = 0);
 
 int linear_f32_dual(const void* a, int64_t lda, const void* a2, int64_t lda2, float ca, float cb, int64_t n, int dk, int dj,
                     const float* w, int64_t ldw, int trans_w, const float* bias, void* out, int64_t ldo, void* out2,
-                    int64_t ldo2, float co, float co2, int in16, int out16, hipStream_t st);
+                    int64_t ldo2, float co, float co2, int in16, int out16, hipStream_t st, int x3 = 0);
 
 }  // namespace sgf

@@ -297,7 +297,7 @@ inline int head_grid(int64_t n) {
 
 int check_head(const char* fn, int64_t n, int d, int c, int dtype) {
   SGF_REQUIRE(n >= 0 && d > 0 && c > 0, SGF_E_INVALID, "%s: bad size", fn);
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     SGF_REQUIRE(linear_f32_supported(d, c), SGF_E_UNSUPPORTED,
                 "%s: fp32 storage needs d and classes multiples of 4 up to 256 (d=%d, classes=%d; pad the class rows of W)", fn, d, c);
     return SGF_OK;
@@ -319,7 +319,7 @@ int check_head(const char* fn, int64_t n, int d, int c, int dtype) {
 using namespace sgf;
 
 extern "C" int32_t sgf_combine_fc_supported(int32_t d, int32_t classes, int32_t dtype) {
-  if (dtype == SGF_F32) return linear_f32_supported(d, classes) ? 1 : 0;   // exact-fp32 matrix cores (csrc/linear_f32.hip)
+  if (f32_storage(dtype)) return linear_f32_supported(d, classes) ? 1 : 0;   // csrc/linear_f32.hip, linear_f32x.hip
   if (dtype != SGF_BF16 || d <= 0 || classes <= 0) return 0;
   if (classes > kMaxClasses) return linear_f32_supported(d, classes) ? 1 : 0;   // the same kernel, bf16 rows in / out
   return d % 32 == 0 && d <= 256 ? 1 : 0;
@@ -333,11 +333,11 @@ static int combine_fc_fwd_impl(const char* fn, const void* x1, int64_t ld1, floa
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(!rmap || (dtype == SGF_BF16 && classes <= kMaxClasses), SGF_E_UNSUPPORTED,
               "%s: a row map needs bf16 storage and at most %d classes", fn, kMaxClasses);
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     SGF_REQUIRE(x1 && x2 && w && logits && ld1 >= d && ld2 >= d && ldl >= classes, SGF_E_INVALID,
                 "%s: bad pointer / ld", fn);
     return linear_f32_dual(x1, ld1, x2, ld2, a, b, n, d, classes, w, d, 1, bias, logits, ldl, nullptr, 0, 1.f, 1.f, 0, 0,
-                           static_cast<hipStream_t>(stream));
+                           static_cast<hipStream_t>(stream), dtype == SGF_F32_BF16X3);
   }
   if (classes > kMaxClasses) {
     SGF_REQUIRE(x1 && x2 && w && logits && ld1 >= d && ld2 >= d && ldl >= classes, SGF_E_INVALID,
@@ -387,11 +387,11 @@ static int combine_fc_bwd_impl(const char* fn, const float* dlogits, int64_t ldd
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(!rmap || (dtype == SGF_BF16 && classes <= kMaxClasses), SGF_E_UNSUPPORTED,
               "%s: a row map needs bf16 storage and at most %d classes", fn, kMaxClasses);
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     SGF_REQUIRE(dlogits && w && dx1 && dx2 && lddl >= classes && ld1 >= d && ld2 >= d, SGF_E_INVALID,
                 "%s: bad pointer / ld", fn);
     return linear_f32_dual(dlogits, lddl, nullptr, 0, 1.f, 0.f, n, classes, d, w, d, 0, nullptr, dx1, ld1, dx2, ld2, a, b, 0, 0,
-                           static_cast<hipStream_t>(stream));
+                           static_cast<hipStream_t>(stream), dtype == SGF_F32_BF16X3);
   }
   if (classes > kMaxClasses) {
     SGF_REQUIRE(dlogits && w && dx1 && dx2 && lddl >= classes && ld1 >= d && ld2 >= d, SGF_E_INVALID,

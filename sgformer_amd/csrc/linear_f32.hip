@@ -12,37 +12,12 @@
 // summation order differs.  Both K-halves drop their accumulator tile into LDS and the epilogue runs row-wise with 16 B
 // per lane: + bias, + addend (the first operand's product of a two-operand Linear), shifted column sums.
 // MFMA-bound at d = 256 (2 n d^2 flop at 155 TF: 2.1 ms at ogbn-products size, against 0.8 ms of HBM time).
-#include "common.h"
+#include "linear_shared.h"
 
 namespace sgf {
 namespace {
 
 constexpr int kLinThreads = 1024;
-
-struct LinArgs {
-  const float* a;
-  int64_t lda;
-  const float* w;          // trans_w = 1: B[k][j] = w[j * ldw + k] (y = x W^T);  0: B[k][j] = w[k * ldw + j] (dx = dy W)
-  int64_t ldw;
-  int32_t trans_w;
-  const float* bias;       // [dj] or null
-  const float* addend;     // [n, dj] or null
-  int64_t ldadd;
-  const float* shift;      // [dj] or null (statistics are of out - shift)
-  float* out;
-  int64_t ldo;
-  int64_t n;
-  int32_t dk, dj;
-  float* spart;            // [gridDim.x][2 * dj] per-block column sums / sums of squares, or null
-  // DUAL form (T7 for fp32 storage, large/ours.py:269-275): the A operand is ca * a + cb * a2, formed while the row tile is
-  // staged (a2 != null), and / or the result leaves twice, co * v -> out and co2 * v -> out2 (out2 != null)
-  const float* a2;
-  int64_t lda2;
-  float ca, cb;
-  float* out2;
-  int64_t ldo2;
-  float co, co2;
-};
 
 __device__ __forceinline__ float4 zero4f() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
@@ -215,7 +190,7 @@ int linear_f32_blocks(int64_t n) {
 // out [n, dj] = a [n, dk] B (+ bias) (+ addend);  spart != null: per-block shifted column sums [blocks][2 * dj]
 int linear_f32(const float* a, int64_t lda, int64_t n, int dk, int dj, const float* w, int64_t ldw, int trans_w,
                const float* bias, const float* addend, int64_t ldadd, const float* shift, float* out, int64_t ldo,
-               float* spart, hipStream_t st) {
+               float* spart, hipStream_t st, int x3) {
   SGF_REQUIRE(linear_f32_supported(dk, dj), SGF_E_UNSUPPORTED, "linear_f32: widths %d -> %d (multiples of 4, <= 256)", dk, dj);
   SGF_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && (!addend || ldadd % 4 == 0) && reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(out) % 16 == 0 && (!addend || reinterpret_cast<uintptr_t>(addend) % 16 == 0) &&
@@ -226,6 +201,7 @@ int linear_f32(const float* a, int64_t lda, int64_t n, int dk, int dj, const flo
   const int blocks = linear_f32_blocks(n);
   const int dmax = dk > dj ? dk : dj;
   const int DP = dmax <= 64 ? 64 : (dmax <= 128 ? 128 : 256);
+  if (x3) return linear_f32x_launch(p, DP, spart != nullptr, false, blocks, st);   // csrc/linear_f32x.hip
 #define SGF_LIN(DP_)                                                                                              \
   do {                                                                                                            \
     if (spart) hipLaunchKernelGGL((k_linear_f32<DP_, true>), dim3(blocks), dim3(kLinThreads), 0, st, p);          \
@@ -243,7 +219,7 @@ int linear_f32(const float* a, int64_t lda, int64_t n, int dk, int dj, const flo
 // in16: a / a2 point at bf16 rows (lda, lda2 in bf16 elements); out16: out / out2 receive bf16 (ldo, ldo2 in bf16 elements)
 int linear_f32_dual(const void* a, int64_t lda, const void* a2, int64_t lda2, float ca, float cb, int64_t n, int dk, int dj,
                     const float* w, int64_t ldw, int trans_w, const float* bias, void* out, int64_t ldo, void* out2,
-                    int64_t ldo2, float co, float co2, int in16, int out16, hipStream_t st) {
+                    int64_t ldo2, float co, float co2, int in16, int out16, hipStream_t st, int x3) {
   SGF_REQUIRE(linear_f32_supported(dk, dj), SGF_E_UNSUPPORTED, "linear_f32: widths %d -> %d (multiples of 4, <= 256)", dk, dj);
   const uintptr_t ain = in16 ? 8 : 16, aout = out16 ? 8 : 16;
   SGF_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && (!a2 || lda2 % 4 == 0) && (!out2 || ldo2 % 4 == 0) &&
@@ -251,11 +227,13 @@ int linear_f32_dual(const void* a, int64_t lda, const void* a2, int64_t lda2, fl
                   (!a2 || reinterpret_cast<uintptr_t>(a2) % ain == 0) && (!out2 || reinterpret_cast<uintptr_t>(out2) % aout == 0) &&
                   (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0),
               SGF_E_INVALID, "linear_f32: rows must be 16-byte aligned (8-byte for bf16 rows)");
-  SGF_REQUIRE(!(in16 && out16) && (!out16 || out2), SGF_E_UNSUPPORTED, "linear_f32_dual: unsupported storage combination");
+  SGF_REQUIRE(!(in16 && out16) && (!out16 || out2) && !(x3 && (in16 || out16)), SGF_E_UNSUPPORTED,
+              "linear_f32_dual: unsupported storage combination");
   LinArgs p{static_cast<const float*>(a), lda, w, ldw, trans_w, bias, nullptr, 0, nullptr, static_cast<float*>(out), ldo, n, dk,
             dj, nullptr, static_cast<const float*>(a2), lda2, ca, cb, static_cast<float*>(out2), ldo2, co, co2};
   const int blocks = linear_f32_blocks(n);
   const int dmax = dk > dj ? dk : dj;
+  if (x3) return linear_f32x_launch(p, dmax <= 64 ? 64 : (dmax <= 128 ? 128 : 256), false, true, blocks, st);
 #define SGF_LIN_DUAL(DP_)                                                                                                  \
   do {                                                                                                                     \
     if (in16) hipLaunchKernelGGL((k_linear_f32<DP_, false, true, true, false>), dim3(blocks), dim3(kLinThreads), 0, st, p);  \

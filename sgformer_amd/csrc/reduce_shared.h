@@ -24,6 +24,12 @@ int gramx_gram(const void* a, int64_t lda, int m, const void* b, int64_t ldb, co
 int gramx_bwdhs(const void* h, int64_t ldh, const void* g, int64_t ldg, const float* rowscal, int d, int64_t n, float* partial,
                 int* nblk, hipStream_t st);
 
+// ---- csrc/gram_f32x.hip: the same plain Gram over two fp32 operands as three bf16 products (SGF_F32_BF16X3) ----
+// (partials in the layout above with DP = 256, RG = 1; rows 16-byte aligned, m, k multiples of 4 up to 256)
+bool gram_f32x_supported(const void* a, int64_t lda, int m, const void* b, int64_t ldb, int k);
+int gram_f32x(const float* a, int64_t lda, int m, const float* b, int64_t ldb, int k, int64_t n, float* partial, int* nblk,
+              hipStream_t st);
+
 // the stems' dW / db with the A operand formed in LDS from the streamed tensors (k_gramt): BatchNorm / LayerNorm backward;
 // every tensor operand 16-byte aligned with ld % 8 == 0 (gramt_aligned), k <= 128.  LN: second / third vector = dbeta / dgamma
 bool gramt_supported(int m, int k, int64_t n);

@@ -1496,7 +1496,7 @@ int launch_rowgemm(const RowGemmArgs& a, int d, int blocks, hipStream_t st) {
 }
 
 bool supported(int32_t d_in, int32_t d_out, int32_t dtype) {
-  if (dtype == SGF_F32) return linear_f32_supported(d_in, d_out);   // fp32 storage: csrc/linear_f32.hip
+  if (f32_storage(dtype)) return linear_f32_supported(d_in, d_out);   // fp32 storage: csrc/linear_f32.hip, linear_f32x.hip
   return dtype == SGF_BF16 && d_in == d_out && (d_in == 64 || d_in == 128 || d_in == 256);
 }
 
@@ -1508,7 +1508,7 @@ int check_common(const char* who, const void* a, int64_t lda, const void* w, int
               "(got %d -> %d, dtype %d)", who, d_in, d_out, dtype);
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(a && w && y, SGF_E_INVALID, "%s: null pointer", who);
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     SGF_REQUIRE(lda >= d_in && ldy >= d_out && lda % 4 == 0 && ldy % 4 == 0 && ldw % 4 == 0 &&
                     reinterpret_cast<uintptr_t>(a) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0,
                 SGF_E_INVALID, "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 4 elements)", who);
@@ -1607,7 +1607,7 @@ extern "C" int sgf_gcn_epilogue_stats(const void* a, int64_t lda, const void* w,
     if (stats) SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * static_cast<size_t>(d_out) * sizeof(float), st));
     return SGF_OK;
   }
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     float* spart = nullptr;
     if (stats) {
       SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
@@ -1615,7 +1615,7 @@ extern "C" int sgf_gcn_epilogue_stats(const void* a, int64_t lda, const void* w,
       spart = static_cast<float*>(workspace);
     }
     rc = linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, bias, nullptr,
-                    0, shift, static_cast<float*>(y), ldy, spart, st);
+                    0, shift, static_cast<float*>(y), ldy, spart, st, dtype == SGF_F32_BF16X3);
     if (rc != SGF_OK || !stats) return rc;
     hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, spart, linear_f32_blocks(n),
                        2 * d_out, stats);
@@ -1643,9 +1643,10 @@ extern "C" int sgf_gcn_epilogue_dx(const void* dy, int64_t lddy, const void* w, 
   int rc = check_common("sgf_gcn_epilogue_dx", dy, lddy, w, ldw, n, d_out, d_in, dtype, dx, lddx);
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
-  if (dtype == SGF_F32)
+  if (f32_storage(dtype))
     return linear_f32(static_cast<const float*>(dy), lddy, n, d_out, d_in, static_cast<const float*>(w), ldw, 0, nullptr,
-                      nullptr, 0, nullptr, static_cast<float*>(dx), lddx, nullptr, static_cast<hipStream_t>(stream));
+                      nullptr, 0, nullptr, static_cast<float*>(dx), lddx, nullptr, static_cast<hipStream_t>(stream),
+                      dtype == SGF_F32_BF16X3);
   RowGemmArgs args{static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(w), ldw, 1, nullptr, nullptr,
                    nullptr, static_cast<uint16_t*>(dx), lddx, n, nullptr};
   return launch_rowgemm<false, 0>(args, d_in, grid_blocks(n), static_cast<hipStream_t>(stream));
@@ -1664,7 +1665,7 @@ extern "C" int sgf_gcn_epilogue_dx2(const void* dy, int64_t lddy, const void* w1
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32 || !pair || grid_blocks(n) < 16) {
+  if (f32_storage(dtype) || !pair || grid_blocks(n) < 16) {
     rc = sgf_gcn_epilogue_dx(dy, lddy, w1, ldw, n, d, d, dtype, dx1, lddx1, stream);
     if (rc != SGF_OK) return rc;
     return sgf_gcn_epilogue_dx(dy, lddy, w2, ldw, n, d, d, dtype, dx2, lddx2, stream);
@@ -1847,7 +1848,7 @@ extern "C" size_t sgf_gcn_epilogue_partial_bytes(int64_t n, int32_t d_out) {
 
 // fp32 storage parks the first operand's product as a plain [n, d_out] fp32 matrix
 extern "C" size_t sgf_gcn_epilogue_dtype_partial_bytes(int64_t n, int32_t d_out, int32_t dtype) {
-  if (dtype == SGF_F32) return n < 0 || d_out <= 0 ? 0 : static_cast<size_t>(n) * static_cast<size_t>(d_out) * 4;
+  if (f32_storage(dtype)) return n < 0 || d_out <= 0 ? 0 : static_cast<size_t>(n) * static_cast<size_t>(d_out) * 4;
   return sgf_gcn_epilogue_partial_bytes(n, d_out);
 }
 
@@ -1860,9 +1861,10 @@ extern "C" int sgf_gcn_epilogue_partial(const void* a, int64_t lda, const void* 
   SGF_REQUIRE(partial_bytes >= sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype), SGF_E_WORKSPACE,
               "sgf_gcn_epilogue_partial: partial buffer %zu < %zu", partial_bytes,
               sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype));
-  if (dtype == SGF_F32)
+  if (f32_storage(dtype))
     return linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, bias, nullptr,
-                      0, nullptr, static_cast<float*>(partial), d_out, nullptr, static_cast<hipStream_t>(stream));
+                      0, nullptr, static_cast<float*>(partial), d_out, nullptr, static_cast<hipStream_t>(stream),
+                      dtype == SGF_F32_BF16X3);
   RowGemmArgs args{static_cast<const uint16_t*>(a), lda, static_cast<const uint16_t*>(w), ldw, 0, bias, nullptr,
                    nullptr, nullptr, 0, n, static_cast<uint4*>(partial)};
   return launch_rowgemm<false, 1>(args, d_out, grid_blocks(n), static_cast<hipStream_t>(stream));
@@ -1882,7 +1884,7 @@ extern "C" int sgf_gcn_epilogue_stats_add(const void* a, int64_t lda, const void
   SGF_REQUIRE(partial && reinterpret_cast<uintptr_t>(partial) % 16 == 0 &&
                   partial_bytes >= sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype),
               SGF_E_INVALID, "sgf_gcn_epilogue_stats_add: partial buffer missing, misaligned or too small");
-  if (dtype == SGF_F32) {
+  if (f32_storage(dtype)) {
     float* spart = nullptr;
     if (stats) {
       SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
@@ -1890,7 +1892,8 @@ extern "C" int sgf_gcn_epilogue_stats_add(const void* a, int64_t lda, const void
       spart = static_cast<float*>(workspace);
     }
     rc = linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, nullptr,
-                    static_cast<const float*>(partial), d_out, shift, static_cast<float*>(y), ldy, spart, st);
+                    static_cast<const float*>(partial), d_out, shift, static_cast<float*>(y), ldy, spart, st,
+                    dtype == SGF_F32_BF16X3);
     if (rc != SGF_OK || !stats) return rc;
     hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, spart, linear_f32_blocks(n),
                        2 * d_out, stats);

@@ -234,7 +234,9 @@ def maybe_step(model, x, edge_index, cdt, out_dtype):
     per_model = model.__dict__.get("_sgf_graphed")
     if per_model is None:
         per_model = model.__dict__["_sgf_graphed"] = _PerModel()
-    key = (int(x.shape[0]), int(x.shape[1]), x.dtype, cdt, out_dtype, x.device)
+    # the fp32 matmul precision picks the kernels (kernels.f32_matmul_code): a step captured under one setting is never
+    # replayed under another
+    key = (int(x.shape[0]), int(x.shape[1]), x.dtype, cdt, out_dtype, x.device, torch.get_float32_matmul_precision())
     entry = per_model.get(key)
     if entry is None:
         entry = per_model[key] = _Entry()

@@ -38,6 +38,37 @@ def _code(t: torch.Tensor) -> int:
     raise TypeError(f"sgformer_amd kernels take float32 or bfloat16 storage, got {t.dtype}")
 
 
+# torch.set_float32_matmul_precision('high' | 'medium') (also set by torch.backends.cuda.matmul.allow_tf32 = True and by
+# TORCH_ALLOW_TF32_CUBLAS_OVERRIDE=1) allows fp32 matrix products "as the sum of two bfloat16 numbers": the entries that
+# accept SGF_F32_BF16X3 then form them as three bf16 matrix-core products (include/sgf.h).  This module is the only place
+# that reads the setting.  torch.get_float32_matmul_precision() is the source of truth: on torch 2.10 the newer
+# torch.backends.cuda.matmul.fp32_precision = 'ieee' does not reset it, so set the precision itself to go back.
+_X3_PRECISIONS = ("high", "medium")
+
+
+def f32_matmul_code() -> int:
+    """The dtype code of fp32 matrix products under the current torch setting: SGF_F32_BF16X3 or SGF_F32."""
+    return _lib.SGF_F32_BF16X3 if torch.get_float32_matmul_precision() in _X3_PRECISIONS else _lib.SGF_F32
+
+
+_x3_cache: "dict[tuple, bool]" = {}
+
+
+def _mm_code(t: torch.Tensor, query: Optional[str] = None, *shape) -> int:
+    """_code(t) for an operand of a matrix product: fp32 storage asks for SGF_F32_BF16X3 when the setting allows it and
+    the entry's *_supported query (if it has one) accepts the code for this shape; otherwise SGF_F32."""
+    code = _code(t)
+    if code != _lib.SGF_F32 or f32_matmul_code() != _lib.SGF_F32_BF16X3:
+        return code
+    if query is None:
+        return _lib.SGF_F32_BF16X3
+    key = (query,) + tuple(int(v) for v in shape)
+    ok = _x3_cache.get(key)
+    if ok is None:
+        ok = _x3_cache[key] = bool(getattr(_lib.load(), query)(*key[1:], _lib.SGF_F32_BF16X3))
+    return _lib.SGF_F32_BF16X3 if ok else _lib.SGF_F32
+
+
 def _ld(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else t.stride(0)
 
@@ -624,7 +655,7 @@ class HipKernels:
         cs = torch.empty(m, dtype=_F32, device=dev) if want_colsum else None
         ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
         with torch.cuda.device(dev):
-            _lib.call("sgf_gram", _ptr(a), _ld(a), m, _ptr(b), _ld(b), k, n, _code(a), _ptr(out),
+            _lib.call("sgf_gram", _ptr(a), _ld(a), m, _ptr(b), _ld(b), k, n, _mm_code(a), _ptr(out),
                       out.stride(0), _ptr(cs), _ptr(ws), ws.numel(), _stream(dev))
         return out, cs
 
@@ -637,7 +668,7 @@ class HipKernels:
         cs = torch.empty(m, dtype=_F32, device=dev) if want_colsum else None
         ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
         with torch.cuda.device(dev):
-            _lib.call("sgf_gram2", _ptr(a), _ld(a), m, _ptr(b1), _ld(b1), _ptr(b2), _ld(b2), k, n, _code(a), _ptr(out1),
+            _lib.call("sgf_gram2", _ptr(a), _ld(a), m, _ptr(b1), _ld(b1), _ptr(b2), _ld(b2), k, n, _mm_code(a), _ptr(out1),
                       out1.stride(0), _ptr(out2), out2.stride(0), _ptr(cs), _ptr(ws), ws.numel(), _stream(dev))
         return cs
 
@@ -893,7 +924,8 @@ class HipKernels:
         with torch.cuda.device(x1.device):
             if row_map is None:
                 _lib.call("sgf_combine_fc_fwd", _ptr(x1), _ld(x1), float(a), _ptr(x2), _ld(x2), float(b), _ptr(w),
-                          _ptr(bias), n, d, c, _code(x1), _ptr(logits), logits.stride(0), _stream(x1.device))
+                          _ptr(bias), n, d, c, _mm_code(x1, "sgf_combine_fc_supported", d, c), _ptr(logits),
+                          logits.stride(0), _stream(x1.device))
             else:
                 _lib.call("sgf_combine_fc_fwd_mapped", _ptr(x1), _ld(x1), float(a), _ptr(x2), _ld(x2), float(b), _ptr(w),
                           _ptr(bias), n, d, c, _code(x1), _ptr(logits), logits.stride(0), _ptr(row_map), _stream(x1.device))
@@ -910,7 +942,7 @@ class HipKernels:
         with torch.cuda.device(g.device):
             if row_map is None:
                 _lib.call("sgf_combine_fc_bwd", _ptr(g), g.stride(0), _ptr(w), n, d, c, float(a), float(b),
-                          _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32, _ptr(dx1), dx1.stride(0), _ptr(dx2),
+                          _mm_code(dx1, "sgf_combine_fc_supported", d, c), _ptr(dx1), dx1.stride(0), _ptr(dx2),
                           dx2.stride(0), _stream(g.device))
             else:
                 _lib.call("sgf_combine_fc_bwd_mapped", _ptr(g), g.stride(0), _ptr(w), n, d, c, float(a), float(b),
@@ -963,7 +995,7 @@ class HipKernels:
         ws = _workspace(dev, "gcn_epi", lib.sgf_gcn_epilogue_workspace_bytes(n, d_out)) if want_stats else None
         with torch.cuda.device(dev):
             _lib.call("sgf_gcn_epilogue_stats", _ptr(a), _ld(a), _ptr(w), w.stride(0), _ptr(bias), n, d_in, d_out,
-                      _code(a), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
+                      _mm_code(a, "sgf_gcn_epilogue_supported", d_in, d_out), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
                       0 if ws is None else ws.numel(), _stream(dev))
         return y, stats
 
@@ -994,9 +1026,9 @@ class HipKernels:
         w1, w2 = w[:, :d1], w[:, d1:]
         with torch.cuda.device(dev):
             _lib.call("sgf_gcn_epilogue_partial", _ptr(a1), _ld(a1), _ptr(w1), w.stride(0), _ptr(bias), n, d1, d,
-                      _code(a1), _ptr(part), part.numel(), _stream(dev))
+                      _mm_code(a1, "sgf_gcn_epilogue_supported", d1, d), _ptr(part), part.numel(), _stream(dev))
             _lib.call("sgf_gcn_epilogue_stats_add", _ptr(a2), _ld(a2), _ptr(w2), w.stride(0), _ptr(part),
-                      part.numel(), n, d2, d, _code(a2), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
+                      part.numel(), n, d2, d, _mm_code(a2, "sgf_gcn_epilogue_supported", d2, d), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
                       0 if ws is None else ws.numel(), _stream(dev))
         return y, stats
 
@@ -1029,7 +1061,8 @@ class HipKernels:
         d_in = w.shape[1]
         dx = torch.empty((n, d_in), dtype=dy.dtype, device=dy.device)
         with torch.cuda.device(dy.device):
-            _lib.call("sgf_gcn_epilogue_dx", _ptr(dy), _ld(dy), _ptr(w), w.stride(0), n, d_in, d_out, _code(dy),
+            _lib.call("sgf_gcn_epilogue_dx", _ptr(dy), _ld(dy), _ptr(w), w.stride(0), n, d_in, d_out,
+                      _mm_code(dy, "sgf_gcn_epilogue_supported", d_out, d_in),
                       _ptr(dx), _ld(dx), _stream(dy.device))
         return dx
 
@@ -1082,7 +1115,8 @@ class HipKernels:
         dx2 = torch.empty((n, d), dtype=dy.dtype, device=dy.device)
         assert w1.stride(0) == w2.stride(0)
         with torch.cuda.device(dy.device):
-            _lib.call("sgf_gcn_epilogue_dx2", _ptr(dy), _ld(dy), _ptr(w1), _ptr(w2), w1.stride(0), n, d, _code(dy),
+            _lib.call("sgf_gcn_epilogue_dx2", _ptr(dy), _ld(dy), _ptr(w1), _ptr(w2), w1.stride(0), n, d,
+                      _mm_code(dy, "sgf_gcn_epilogue_supported", d, d),
                       _ptr(dx1), _ld(dx1), _ptr(dx2), _ld(dx2), int(pair), _stream(dy.device))
         return dx1, dx2
 

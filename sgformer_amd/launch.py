@@ -18,6 +18,9 @@ activation storage (fp32 master weights / accumulation); the default is the refe
 For `main-batch.py` the per-batch `torch_geometric.utils.subgraph` call is served by the GPU
 implementation in sgformer_amd.batching (`--sgf-host-subgraph 1` keeps PyG's host version).  The trainers' own
 `nn.NLLLoss()` runs as a gather + masked sum instead of ATen's one-block reduction (`--sgf-aten-loss 1` keeps ATen's).
+`--sgf-f32-matmul {highest,high,medium}` calls torch.set_float32_matmul_precision before the trainer runs (the trainers
+never set it themselves): under 'high' / 'medium' the fp32 Linear layers and weight gradients run as three bf16
+matrix-core products; the default leaves torch's setting alone.
 
 What the launcher rewires besides `ours`, and how to turn each off (every patch reaches the original for any call it does not
 cover; tests/test_launch_patches.py drives each with callers that are not the reference's trainers):
@@ -304,8 +307,25 @@ def _pop_option(argv, name):
     return None
 
 
+F32_MATMUL = ("highest", "high", "medium")
+
+
+def apply_f32_matmul(argv):
+    """Remove `--sgf-f32-matmul VALUE` from argv and hand VALUE to torch.set_float32_matmul_precision; returns VALUE (None:
+    the option is absent and torch's setting is left alone)."""
+    v = _pop_option(argv, "--sgf-f32-matmul")
+    if v is None:
+        return None
+    if v not in F32_MATMUL:
+        raise SystemExit(f"sgformer_amd.launch: --sgf-f32-matmul {v!r} (choose from {', '.join(F32_MATMUL)})")
+    import torch
+    torch.set_float32_matmul_precision(v)
+    return v
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
+    apply_f32_matmul(argv)
     variant = _pop_option(argv, "--sgf-variant")
     dtype = _pop_option(argv, "--sgf-dtype")
     host_subgraph = _pop_option(argv, "--sgf-host-subgraph")   # any value: keep PyG's host subgraph
