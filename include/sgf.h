@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 610 /* 0.6.1: dtype code SGF_F32_BF16X3, accepted by the fp32 Linear entries (sgf_gcn_epilogue_stats, _dx, _dx2, _partial, _stats_add, sgf_combine_fc_fwd / _bwd) and by sgf_gram / sgf_gram2 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 620 /* 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -861,6 +861,42 @@ int sgf_nll_fwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t d
                 void* workspace, size_t workspace_bytes, void* stream);
 int sgf_nll_bwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype,
                 const int64_t* labels, const int64_t* idx, int64_t m, const float* gout,
+                float inv_denom, void* dlogits, int64_t ldd, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N4b — the trainer's OTHER loss, for the multi-label / binary data sets (ogbn-proteins, deezer-europe, twitch-e, fb100,
+ * yelp-chi).   Replaces large/main.py:130-137 (= large/main-batch.py:101-105, medium/main.py:158-166)
+ *     loss = BCEWithLogitsLoss()(out[train_idx], true_label.squeeze(1)[train_idx].to(torch.float))
+ * (a row-index kernel, a cast, the element-wise chain of binary_cross_entropy_with_logits, a mean, and in the backward an
+ * index_put scatter back to [N, C]) as one pass over the M training rows:
+ *     sgf_bce_fwd : loss_sum[0] = inv_denom * sum_j sum_k l(x[r_j, k], t[r_j, k]),
+ *                   l(x, t) = max(x, 0) - x t + log1p(exp(-|x|)),   r_j = idx[j]
+ *                   (fp32; the caller chooses the divisor: inv_denom = 1 / (M * C), 1 / (GLOBAL count * C) when
+ *                   node-sharded, or 1 for the plain sum — one multiplication of the finished sum, no launch of its own)
+ *     sgf_bce_bwd : dlogits = 0 everywhere except rows r_j, where
+ *                   dlogits[r_j, k] = gout[0] * inv_denom * (sigmoid(x[r_j, k]) - t[r_j, k])
+ * logits / dlogits: [n, c] in the storage dtype (SGF_F32 or SGF_BF16) with leading dims ldl / ldd, any c >= 1; all
+ * arithmetic and the accumulation are fp32 (expf / log1pf, no fast intrinsics), the gradient is rounded once to the storage
+ * dtype.  idx: int64 [m] distinct rows in [0, n); idx == NULL is the DENSE form, rows 0..m-1 with m == n (one streaming
+ * pass; equal to the row form with idx = 0..n-1 bit for bit).  gout fp32 [1] on the device.
+ * target is indexed by NODE id (as the labels of sgf_nll_*) and read as it is stored, without a cast pass:
+ *     SGF_BCE_TARGET_F32   : fp32  [n, c], leading dim ldt; soft targets allowed
+ *     SGF_BCE_TARGET_I64   : int64 [n, c] of 0 / 1, leading dim ldt (F.one_hot's result, the ogbn-proteins labels)
+ *     SGF_BCE_TARGET_CLASS : int64 [n] class indices, the one-hot row formed on the fly (ldt is ignored).  An index outside
+ *                            [0, c) matches no column: that row's target is all zero.  The index is only compared, never
+ *                            used as an address, and nothing is validated on the host.
+ * 16-byte accesses when c % 4 == 0 and every operand's rows start on a 4-element boundary; one element per lane otherwise.
+ * Deterministic (fixed per-thread order, fixed block tree, fixed-order sum of the per-block partials).
+ * ------------------------------------------------------------------------------------------ */
+#define SGF_BCE_TARGET_F32 0
+#define SGF_BCE_TARGET_I64 1
+#define SGF_BCE_TARGET_CLASS 2
+size_t sgf_bce_workspace_bytes(int64_t m, int32_t c);
+int sgf_bce_fwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* target,
+                int64_t ldt, int32_t target_kind, const int64_t* idx, int64_t m, float inv_denom,
+                float* loss_sum, void* workspace, size_t workspace_bytes, void* stream);
+int sgf_bce_bwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* target,
+                int64_t ldt, int32_t target_kind, const int64_t* idx, int64_t m, const float* gout,
                 float inv_denom, void* dlogits, int64_t ldd, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand

@@ -15,6 +15,9 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsgf.so")
 SGF_F32 = 0
 SGF_BF16 = 1
 SGF_F32_BF16X3 = 2   # fp32 storage, matrix products as three bf16 products (include/sgf.h)
+SGF_BCE_TARGET_F32 = 0     # target kinds of sgf_bce_fwd / _bwd: fp32 [n, c]
+SGF_BCE_TARGET_I64 = 1     # int64 0 / 1 [n, c]
+SGF_BCE_TARGET_CLASS = 2   # int64 class indices [n]
 
 _lib = None
 
@@ -148,6 +151,11 @@ SIGNATURES = {
     "sgf_nll_workspace_bytes": (c_size_t, [c_int64]),
     "sgf_nll_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, _P, c_size_t, _P]),
     "sgf_nll_bwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_int64, _P, c_float, _P,
+                              c_int64, _P]),
+    "sgf_bce_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "sgf_bce_fwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, c_float, _P, _P,
+                              c_size_t, _P]),
+    "sgf_bce_bwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, c_float, _P,
                               c_int64, _P]),
     "sgf_sum_n": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64, _P]),
     "sgf_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32]),

@@ -25,7 +25,8 @@ four exchange points, all designed into the kernels' partial-sum layouts:
   parameter grads     ONE flat all-reduce (SUM) per step: each rank's autograd already produces the
                       gradient of the GLOBAL loss w.r.t. its local rows, so parameter gradients are
                       plain sums over ranks
-The loss is normalised by the GLOBAL number of training rows (`sharded_nll_loss`).
+The loss is normalised by the GLOBAL number of training rows (`sharded_nll_loss`; `sharded_bce_loss` for the
+multi-label data sets).
 
 Two input conventions: by default every rank passes the GLOBAL edge_index (the graph is replicated,
 the row block is cut out of the full CSR); with `ShardContext(N, local_edges=True)` a rank passes
@@ -555,3 +556,11 @@ def sharded_nll_loss(logits_local: torch.Tensor, y_local: torch.Tensor, train_id
     """log_softmax + NLL (large/main.py:139-141) summed over the LOCAL training rows and divided by
     the GLOBAL count: the sum over ranks is the full-graph mean loss (fused: ops.nll_loss_rows)."""
     return ops.nll_loss_rows(logits_local, y_local, train_idx_local, denom=n_train_global)
+
+
+def sharded_bce_loss(logits_local: torch.Tensor, target_local: torch.Tensor, train_idx_local: torch.Tensor,
+                     n_train_global: int) -> torch.Tensor:
+    """BCEWithLogitsLoss (large/main.py:130-137) over the local training rows of the multi-label data sets, normalised by
+    the GLOBAL row count times C: the sum over ranks is the full-graph mean loss (fused: ops.bce_loss_rows).  `target_local`:
+    the local rows of the [N, C] target, or of the class indices."""
+    return ops.bce_loss_rows(logits_local, target_local, train_idx_local, denom=n_train_global)

@@ -885,6 +885,80 @@ class HipKernels:
                       _stream(dev))
         return d
 
+    # ---- N4b: BCEWithLogitsLoss on the training rows (idx None: the dense form, every row) ----
+    # These two sit on a path whose GPU work is a few microseconds at mini-batch sizes: the host side is kept to one pass
+    # over the arguments, one allocation and one ctypes call each (constant workspace size cached, no device context
+    # switch when the tensors' device is already current).
+    @staticmethod
+    def _bce_args(logits, target, idx):
+        """(n, c, m, target, kind, ldt) after the checks both entries share: logits [n, c] fp32 / bf16 with unit inner stride
+        and rows that do not overlap; target fp32 or int64 [n, c] (contiguous rows) or int64 [n] class indices; idx int64
+        [m] contiguous or None."""
+        if logits.dim() != 2 or logits.stride(1) != 1 or (logits.stride(0) < logits.shape[1] and logits.shape[0] > 1):
+            raise ValueError(f"bce: logits must be [n, c] with unit inner stride and a row stride >= c, got shape "
+                             f"{tuple(logits.shape)} strides {logits.stride()}")
+        n, c = logits.shape
+        tdt = target.dtype
+        if target.device != logits.device or (idx is not None and idx.device != logits.device):
+            raise ValueError("bce: logits, target and idx must be on the same device")
+        if target.dim() == 2 and target.shape == logits.shape and (tdt == _F32 or tdt == torch.int64):
+            if target.stride(1) != 1 or (target.stride(0) < c and n > 1):
+                raise ValueError(f"bce: target rows must be contiguous, got strides {target.stride()}")
+            kind = _lib.SGF_BCE_TARGET_F32 if tdt == _F32 else _lib.SGF_BCE_TARGET_I64
+            ldt = max(target.stride(0), c)
+        elif target.dim() == 1 and target.shape[0] == n and tdt == torch.int64:
+            kind, ldt = _lib.SGF_BCE_TARGET_CLASS, 0
+            target = target.contiguous()
+        else:
+            raise ValueError(f"bce: target must be float32 / int64 {tuple(logits.shape)} or int64 class indices [{n}], got "
+                             f"{tdt} {tuple(target.shape)}")
+        if idx is None:
+            m = n
+        else:
+            if idx.dim() != 1 or idx.dtype != torch.int64 or not idx.is_contiguous():
+                raise ValueError(f"bce: idx must be a contiguous int64 vector, got {idx.dtype} {tuple(idx.shape)}")
+            m = idx.numel()
+            if m > n:
+                raise ValueError(f"bce: idx holds {m} rows of a {n}-row matrix (rows must be distinct)")
+        return n, c, m, target, kind, ldt
+
+    _bce_ws_bytes = None
+
+    @staticmethod
+    def bce_fwd(logits, target, idx, inv_denom: float = 1.0) -> torch.Tensor:
+        """inv_denom * sum of the element losses over the rows idx, as a 0-dim fp32 tensor."""
+        n, c, m, target, kind, ldt = HipKernels._bce_args(logits, target, idx)
+        dev = logits.device
+        code = _code(logits)
+        out = torch.empty((), dtype=_F32, device=dev)
+        if HipKernels._bce_ws_bytes is None:       # (a constant of the library: the block-partial buffer)
+            HipKernels._bce_ws_bytes = int(_lib.load().sgf_bce_workspace_bytes(m, c))
+        ws = _workspace(dev, "bce", HipKernels._bce_ws_bytes)
+        args = (_ptr(logits), max(logits.stride(0), c), n, c, code, _ptr(target), ldt, kind, _ptr(idx), m, float(inv_denom),
+                _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+        if torch.cuda.current_device() == dev.index:
+            _lib.call("sgf_bce_fwd", *args)
+        else:
+            with torch.cuda.device(dev):
+                _lib.call("sgf_bce_fwd", *args)
+        return out
+
+    @staticmethod
+    def bce_bwd(logits, target, idx, gout, inv_denom: float) -> torch.Tensor:
+        n, c, m, target, kind, ldt = HipKernels._bce_args(logits, target, idx)
+        dev = logits.device
+        if gout.dtype != _F32 or gout.numel() != 1 or gout.device != dev:
+            raise ValueError("bce: gout must be one float32 on the logits' device")
+        d = torch.empty((n, c), dtype=logits.dtype, device=dev)
+        args = (_ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(target), ldt, kind, _ptr(idx), m,
+                _ptr(gout), float(inv_denom), _ptr(d), c, _stream(dev))
+        if torch.cuda.current_device() == dev.index:
+            _lib.call("sgf_bce_bwd", *args)
+        else:
+            with torch.cuda.device(dev):
+                _lib.call("sgf_bce_bwd", *args)
+        return d
+
     @staticmethod
     def sum_n(xs) -> torch.Tensor:
         """sum of up to 8 equally shaped [n, d] tensors in one pass."""

@@ -17,7 +17,8 @@ the libsgf one) — or from --sgf-variant.  `--sgf-dtype bf16` switches every SG
 activation storage (fp32 master weights / accumulation); the default is the reference's fp32.
 For `main-batch.py` the per-batch `torch_geometric.utils.subgraph` call is served by the GPU
 implementation in sgformer_amd.batching (`--sgf-host-subgraph 1` keeps PyG's host version).  The trainers' own
-`nn.NLLLoss()` runs as a gather + masked sum instead of ATen's one-block reduction (`--sgf-aten-loss 1` keeps ATen's).
+`nn.NLLLoss()` runs as a gather + masked sum instead of ATen's one-block reduction, and their `nn.BCEWithLogitsLoss()` (the
+multi-label data sets) as one pass each way (`--sgf-aten-loss 1` keeps ATen's for both).
 `--sgf-f32-matmul {highest,high,medium}` calls torch.set_float32_matmul_precision before the trainer runs (the trainers
 never set it themselves): under 'high' / 'medium' the fp32 Linear layers and weight gradients run as three bf16
 matrix-core products; the default leaves torch's setting alone.
@@ -26,6 +27,8 @@ What the launcher rewires besides `ours`, and how to turn each off (every patch 
 cover; tests/test_launch_patches.py drives each with callers that are not the reference's trainers):
 
     F.log_softmax / F.nll_loss          lazy log-softmax + one-pass loss on the training rows   --sgf-aten-loss 1
+    F.binary_cross_entropy_with_logits  nn.BCEWithLogitsLoss() of the multi-label sets in one pass
+                                        (inputs of >= 2^23 elements; smaller ones stay on ATen)  --sgf-aten-loss 1
     torch.optim.Adam.__init__           fused=True for all-CUDA float parameters                SGF_FUSED_ADAM=0
     torch_geometric.utils.subgraph      device implementation (main-batch.py only)              --sgf-host-subgraph 1
     torch_geometric.utils.to_undirected / remove_self_loops / add_self_loops                    --sgf-host-prologue 1
@@ -230,6 +233,68 @@ def patch_nll_loss():
     return orig
 
 
+# The one-pass criterion is bound from Python (ctypes behind an autograd.Function, whose backward the autograd engine calls
+# from its device thread); ATen's element-wise chain is issued from C++.  At small sizes both are bound by the host, and the
+# Python binding is the slower one; ATen's chain becomes GPU-bound first, and from there the one-pass form wins.  Measured
+# with scripts/bce_probe.py --sweep on MI355X boxes (profiles/bce_probe.md): the crossover depends on
+# the host — between 2 M and 4 M elements of `out[train_idx]` on one box, between 8.0 M (1.01 x) and 9.6 M (0.89 x) on
+# another.  The count below is above both: under it the patch hands the call to the original, so it is never the slower one.
+BCE_PATCH_MIN_ELEMENTS = 1 << 23
+
+
+def patch_bce_loss(min_elements=None):
+    """The multi-label / binary data sets keep their own loss lines too (large/main.py:130-137:
+    `criterion = nn.BCEWithLogitsLoss()` on `out[train_idx]` against `true_label.squeeze(1)[train_idx].to(torch.float)`).
+    ATen runs the criterion as an element-wise chain plus a mean, and as many kernels again in the backward; the dense form
+    of sgf_bce_fwd / sgf_bce_bwd (sgformer_amd.loss.dense_bce) is one pass each way.  Installed behind
+    torch.nn.functional.binary_cross_entropy_with_logits — which nn.BCEWithLogitsLoss.forward looks up at call time — for
+    exactly the case the trainers use: a 2-D CUDA input of fp32 or bf16 with unit inner stride and a row stride of at least its width, a target of the same shape
+    and device in fp32, bf16 or fp16 that does not require a gradient, no weight / pos_weight / size_average / reduce,
+    reduction 'mean', and at least `min_elements` elements (default BCE_PATCH_MIN_ELEMENTS, measured: below it ATen's
+    launches from C++ cost less host time than the Python binding of the two kernels — the ogbn-proteins mini-batch of
+    10 000 nodes stays on ATen, a full-graph step of that data set takes the one-pass form; 0: every size).  Anything else reaches the original with all its arguments (a float64 target
+    among them: torch promotes that loss to float64 arithmetic, which the kernels do not have).  The trainers'
+    `out[train_idx]` stays ATen's indexing; sgformer_amd.loss.bce_with_logits_rows fuses the row gather as well.
+    `--sgf-aten-loss 1` keeps ATen's.  Idempotent."""
+    import torch
+    import torch.nn.functional as F
+    from . import ops
+    from .loss import dense_bce
+    orig = getattr(F.binary_cross_entropy_with_logits, "_sgf_orig", F.binary_cross_entropy_with_logits)
+    least = max(1, BCE_PATCH_MIN_ELEMENTS if min_elements is None else int(min_elements))
+
+    def on_device(t):                       # (the tests drive this with a CPU kernel table)
+        return t.is_cuda if ops.K.name == "hip" else True
+
+    plain = (torch.Tensor, torch.nn.Parameter)
+    logit_types = (torch.float32, torch.bfloat16)
+    target_types = (torch.float32, torch.bfloat16, torch.float16)
+
+    def binary_cross_entropy_with_logits(input, target, weight=None, size_average=None, reduce=None, reduction="mean",
+                                         pos_weight=None):
+        # (cheapest tests first: a call this patch does not take should cost next to nothing on its way to the original)
+        if (weight is None and pos_weight is None and reduction == "mean" and size_average is None and reduce is None
+                and type(input) in plain and type(target) is torch.Tensor and input.numel() >= least
+                and input.dim() == 2 and input.dtype in logit_types and on_device(input)
+                and input.stride(1) == 1 and input.stride(0) >= input.shape[1]
+                and target.shape == input.shape and target.device == input.device and not target.requires_grad
+                and target.dtype in target_types):
+            return dense_bce(input, target)
+        return orig(input, target, weight=weight, size_average=size_average, reduce=reduce, reduction=reduction,
+                    pos_weight=pos_weight)
+
+    binary_cross_entropy_with_logits._sgf_orig = orig
+    F.binary_cross_entropy_with_logits = binary_cross_entropy_with_logits
+    return orig
+
+
+def unpatch_bce_loss():
+    import torch.nn.functional as F
+    orig = getattr(F.binary_cross_entropy_with_logits, "_sgf_orig", None)
+    if orig is not None:
+        F.binary_cross_entropy_with_logits = orig
+
+
 def patch_adam():
     """torch.optim.Adam as the trainers construct it (large/main.py:114-119: two parameter groups, no `fused` / `foreach`
     argument) runs its for-each form: ~12 multi-tensor launches per group and step.  For CUDA parameters torch's own
@@ -331,7 +396,7 @@ def main(argv=None):
     host_subgraph = _pop_option(argv, "--sgf-host-subgraph")   # any value: keep PyG's host subgraph
     host_prologue = _pop_option(argv, "--sgf-host-prologue")   # any value: keep PyG's host to_undirected & co.
     host_features = _pop_option(argv, "--sgf-host-features")   # any value: keep node features on the host
-    aten_loss = _pop_option(argv, "--sgf-aten-loss")           # any value: keep ATen's nll_loss kernels
+    aten_loss = _pop_option(argv, "--sgf-aten-loss")           # any value: keep ATen's nll_loss and BCE kernels
     host_sampler = _pop_option(argv, "--sgf-host-sampler")     # any value: keep PyG's host NeighborLoader (100M)
     patches = _pop_option(argv, "--sgf-patches") or os.environ.get("SGF_PATCHES", "all")
     if patches not in ("all", "minimal"):
@@ -361,7 +426,7 @@ def main(argv=None):
     if patches == "minimal":
         # the module drop-in ONLY: `ours` (and, for the medium / 100M trainers, the two repairs above, which touch the
         # TRAINER's own modules) — nothing of torch, torch_geometric or the host thread pool is rewired: F.log_softmax,
-        # F.nll_loss, torch.optim.Adam, torch_geometric.utils.* and NeighborLoader stay what the environment provides
+        # F.nll_loss, F.binary_cross_entropy_with_logits, torch.optim.Adam, torch_geometric.utils.* and NeighborLoader stay what the environment provides
         runpy.run_path(trainer, run_name="__main__")
         return
     if host_subgraph is None and os.path.basename(trainer) == "main-batch.py":
@@ -374,6 +439,7 @@ def main(argv=None):
         patch_neighbor_loader()
     if aten_loss is None:
         patch_nll_loss()
+        patch_bce_loss()
     patch_adam()
     if os.path.basename(trainer) == "main-batch.py":
         limit_host_threads()

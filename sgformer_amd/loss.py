@@ -8,6 +8,15 @@ is the arithmetic of large/main.py:139-141
 with `criterion = nn.NLLLoss()`) on sgf_nll_fwd / sgf_nll_bwd.  Optional: the unchanged trainers keep
 their own three lines (5 ATen kernels; 4.2 ms of `nll_loss` kernels per step at ogbn-products
 scale); a maintainer who edits those lines gets the fused form.  `bench.py` times the step with it.
+
+The multi-label / binary data sets (ogbn-proteins, deezer-europe, twitch-e, fb100, yelp-chi) take the trainers' other
+criterion, `nn.BCEWithLogitsLoss()` (large/main.py:130-137):
+
+    from sgformer_amd.loss import bce_with_logits_rows
+    loss = bce_with_logits_rows(out, dataset.label, train_idx)
+
+on sgf_bce_fwd / sgf_bce_bwd: row gather, cast, element-wise chain and mean in one pass, the gradient written straight
+into [N, C].  The unchanged trainers get the element-wise part in one pass from sgformer_amd.launch (`dense_bce`).
 """
 from . import ops
 
@@ -15,6 +24,27 @@ from . import ops
 def log_softmax_nll(out, label, train_idx, denom=None):
     """`label` may be [N] or [N, 1] (the trainers keep [N, 1], large/main.py:48-50)."""
     return ops.nll_loss_rows(out, label, train_idx, denom)
+
+
+def bce_with_logits_rows(out, target, train_idx, denom=None):
+    """`BCEWithLogitsLoss()(out[train_idx], true_label.squeeze(1)[train_idx].to(torch.float))` — large/main.py:130-137,
+    large/main-batch.py:101-105 and :144-145, medium/main.py:158-166, large/eval.py:54-59 — with `target` indexed by NODE
+    id: the [N, C] labels as the data set holds them (int64 0 / 1 for ogbn-proteins, float soft targets, bool), or the
+    [N] / [N, 1] class indices the trainers turn into `F.one_hot(label, label.max() + 1)` first (the one-hot row is formed
+    in the kernel, C = out.shape[1]).  `train_idx`: int64 rows, a bool mask over N, or None for every row.  Mean over
+    m * C elements, or `denom` * C."""
+    return ops.bce_loss_rows(out, target, train_idx, denom)
+
+
+def dense_bce(input, target):
+    """F.binary_cross_entropy_with_logits(input, target) — no weights, reduction 'mean' — for a 2-D input and a floating
+    target of its shape, as ONE pass forward and one backward (the dense form of sgf_bce_fwd / _bwd) instead of ATen's
+    element-wise chain and mean.  The result has the dtype torch's type promotion gives the original.  Installed behind
+    torch.nn.functional.binary_cross_entropy_with_logits by sgformer_amd.launch.patch_bce_loss."""
+    loss = ops.bce_loss_rows(input, target, None)                       # fp32
+    if input.dtype == loss.dtype or target.dtype == loss.dtype:        # (promotion with an fp32 operand: fp32)
+        return loss
+    return loss.to(_torch.result_type(input, target))
 
 
 def gather_nll(input, target, ignore_index=-100):

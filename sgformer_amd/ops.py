@@ -453,6 +453,74 @@ def nll_loss_rows(logits, labels, idx, denom=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# N4b: the trainer's other loss, BCEWithLogitsLoss on the training rows (large/main.py:130-137)
+# ------------------------------------------------------------------------------------------------
+def _bce_target(logits, target):
+    """The target as the kernels read it: float32 or int64 [N, C] (multi-hot, soft targets allowed), or int64 class indices
+    [N].  The kind comes from shape and dtype; bool / uint8 / other integer and other floating targets are converted once
+    on the device, float32 and int64 ones are read as they are."""
+    n, c = logits.shape
+    if target.shape == logits.shape:
+        if target.dtype in (_F32, torch.int64):
+            return target if target.is_contiguous() else target.contiguous()
+        if target.is_floating_point() or target.dtype == torch.bool:
+            return target.to(_F32).contiguous()
+        if not target.is_complex():
+            return target.to(torch.int64).contiguous()
+    elif (c > 1 and target.numel() == n and target.shape in ((n,), (n, 1)) and not target.is_floating_point()
+          and not target.is_complex() and target.dtype != torch.bool):
+        return target.reshape(-1).to(torch.int64).contiguous()
+    raise ValueError(f"bce_loss_rows: cannot read a {target.dtype} target of shape {tuple(target.shape)} for logits "
+                     f"{tuple(logits.shape)}: pass a [N, C] multi-hot / soft target, or integer class indices [N] or [N, 1] "
+                     "(C > 1)")
+
+
+class _BceRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, idx, denom):
+        K.check(logits, target, idx)
+        if logits.dim() != 2:
+            raise ValueError(f"bce_loss_rows: logits must be [N, C], got {tuple(logits.shape)}")
+        n, c = logits.shape
+        if logits.stride(1) != 1 or (logits.stride(0) < c and n > 1):       # (expanded / overlapping rows: a real copy)
+            logits = logits.contiguous()
+        target = _bce_target(logits, target)
+        if idx is not None:
+            idx = idx.contiguous()
+            if idx.dtype == torch.bool:
+                idx = idx.nonzero().view(-1)
+        m = (n if idx is None else idx.numel()) if denom is None else denom
+        ctx.save_for_backward(logits, target, idx)
+        ctx.inv = 1.0 / (float(max(m, 1)) * c)
+        return K.bce_fwd(logits, target, idx, ctx.inv)             # (0-dim, already divided: no launch besides the kernels')
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():      # (only under create_graph=True)
+            # sgf_bce_bwd has no graph of its own: a caller who wants to differentiate this gradient again (a gradient
+            # penalty) must hear so, not receive a gradient that silently is a constant
+            raise RuntimeError("sgformer_amd: the one-pass BCE-with-logits loss is once differentiable; backward with "
+                               "create_graph=True is not implemented (run the launcher with --sgf-aten-loss 1, or call "
+                               "launch.unpatch_bce_loss(), to keep ATen's twice differentiable loss)")
+        logits, target, idx = ctx.saved_tensors
+        if g.dtype != _F32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        return K.bce_bwd(logits, target, idx, g, ctx.inv), None, None, None
+
+
+def bce_loss_rows(logits, target, idx, denom=None):
+    """mean over the rows `idx` and all C columns of  max(x, 0) - x t + log1p(exp(-|x|))  ==  the lines
+    large/main.py:130-137 (`nn.BCEWithLogitsLoss()` on `out[train_idx]` against
+    `true_label.squeeze(1)[train_idx].to(torch.float)`) in one pass over the training rows.  `idx`: int64 rows (distinct),
+    a bool mask over N, or None for every row (the dense form).  `target` is indexed by NODE id: [N, C] multi-hot (float32
+    and int64 are read as stored; soft targets allowed) or integer class indices [N] / [N, 1] with C > 1, whose one-hot row
+    is formed in the kernel — an index outside [0, C) matches no column (an all-zero row; nothing is validated).  The
+    divisor is m * C, or `denom` * C (the GLOBAL training-row count of a node-sharded run); no rows: loss 0, zero gradient.
+    fp32 math on fp32 or bf16 logits; the gradient is written for all N rows (zeros off the training rows)."""
+    return _BceRows.apply(logits, target, idx, denom)
+
+
+# ------------------------------------------------------------------------------------------------
 # row permutation at the module boundary (re-ordered graphs) and mini-batch row gathers
 # ------------------------------------------------------------------------------------------------
 class _PermuteRows(torch.autograd.Function):
