@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 620 /* 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 630 /* 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -464,8 +464,13 @@ int sgf_attn_bwd_apply_heads(const void* q, int64_t ldq, const void* k, int64_t 
  * all-reduce [G | s] and hstats (d^2 + d and d^2 + 2d + 1 floats).
  * M, D: fp32 [d, d] row-major (M[k][j]: input feature k -> output feature j); m, w, ds: fp32 [d];
  * beta: fp32 [1]; all DEVICE pointers.  d % 4 == 0, d <= 256.
+ * These three entries accept SGF_F32_BF16X3 (sgf_attn_h_supported): h M, dnum M^T, h D and h^T dnum are then formed as
+ * three bf16 products; the row dots h.w and g.out, 1 / den, dnum, dden, the vector sums of hstats and the vectors m, w, ds
+ * stay exact fp32 (den is the SGF_F32 value up to summation order).  Same tensors, same workspaces as SGF_F32.
  * ------------------------------------------------------------------------------------------ */
 int64_t sgf_attn_h_bstats_len(int32_t d);
+/* 1 where sgf_attn_h_fwd / _bwd_reduce / _bwd_apply run head dim `d` under dtype code `dtype`, else 0 (host query) */
+int32_t sgf_attn_h_supported(int32_t d, int32_t dtype);
 int sgf_attn_h_fwd(const void* h, int64_t ldh, int64_t n, int32_t d, int32_t dtype, const float* M,
                    const float* m, const float* w, const float* beta, void* out, int64_t ldo,
                    float* den, void* stream);
@@ -477,7 +482,8 @@ int sgf_attn_h_bwd_apply(const void* h, int64_t ldh, const void* g, int64_t ldg,
                          const float* M, const float* w, const float* D, const float* ds, void* dh,
                          int64_t lddh, void* workspace, size_t workspace_bytes, void* stream);
 /* scratch of sgf_attn_h_bwd_apply: bf16 storage with d in {64, 128, 256} runs as two per-wave streaming passes
- * (csrc/rowgemm.hip) with the first product parked in the matrix cores' accumulator layout; 0 otherwise */
+ * (csrc/rowgemm.hip) with the first product parked in the matrix cores' accumulator layout; 0 otherwise (fp32 storage
+ * under either code needs none) */
 size_t sgf_attn_h_bwd_apply_workspace_bytes(int64_t n, int32_t d, int32_t dtype);
 /* The same backward as three calls (bf16 storage, d in {64, 128, 256}: sgf_attn_h_bwd_split_supported), ordered so that
  * the node reduction can use what the first apply pass computes anyway:
@@ -489,7 +495,8 @@ size_t sgf_attn_h_bwd_apply_workspace_bytes(int64_t n, int32_t d, int32_t dtype)
  *                                   dim ldadd): a second gradient of h — the residual branch's, large/ours.py:206-208 uses
  *                                   the layer input twice — added to the rounded result here instead of in a separate
  *                                   three-tensor pass.
- * sgf_attn_h_bwd_reduce + sgf_attn_h_bwd_apply remain for everything else. */
+ * sgf_attn_h_bwd_reduce + sgf_attn_h_bwd_apply remain for everything else; these three calls and the query reject
+ * SGF_F32_BF16X3. */
 int32_t sgf_attn_h_bwd_split_supported(int32_t d, int32_t dtype);
 int sgf_attn_h_bwd_pre(const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den, int64_t n, int32_t d,
                        int32_t dtype, const float* M, const float* w, void* workspace, size_t workspace_bytes,

@@ -103,6 +103,7 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, c_int64, _P, c_size_t, _P]),
     "sgf_attn_h_bwd_apply_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "sgf_attn_h_bwd_split_supported": (c_int32, [c_int32, c_int32]),
+    "sgf_attn_h_supported": (c_int32, [c_int32, c_int32]),
     "sgf_attn_h_bwd_pre": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P, _P]),
     "sgf_attn_h_bwd_reduce_scaled": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, c_size_t,
                                                _P]),

@@ -1340,6 +1340,11 @@ int check_common(const char* fn, int64_t n, int heads, int d, int dtype) {
   return SGF_OK;
 }
 
+// the three row passes of the attention from the un-projected input also take SGF_F32_BF16X3 (csrc/attn_f32x.hip)
+int check_common_h(const char* fn, int64_t n, int d, int dtype) {
+  return check_common(fn, n, 1, d, dtype == SGF_F32_BF16X3 ? SGF_F32 : dtype);
+}
+
 template <typename T>
 bool aligned4(const void* p, int64_t ld) {
   return reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0 && ld % 4 == 0;
@@ -1714,11 +1719,13 @@ int h_bwd_apply_t(const void* h, int64_t ldh, const void* g, int64_t ldg, const 
 extern "C" int sgf_attn_h_fwd(const void* h, int64_t ldh, int64_t n, int32_t d, int32_t dtype,
                               const float* M, const float* m, const float* w, const float* beta,
                               void* out, int64_t ldo, float* den, void* stream) {
-  int rc = check_common("sgf_attn_h_fwd", n, 1, d, dtype);
+  int rc = check_common_h("sgf_attn_h_fwd", n, d, dtype);
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(h && M && m && w && beta && out && den, SGF_E_INVALID, "sgf_attn_h_fwd: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == SGF_F32_BF16X3)
+    return attn_h_f32x_fwd(static_cast<const float*>(h), ldh, n, d, M, m, w, beta, static_cast<float*>(out), ldo, den, st);
   if (dtype == SGF_F32) return h_fwd_t<float>(h, ldh, n, d, M, m, w, beta, out, ldo, den, st);
   // bf16, d in {64, 128, 256}, 16-byte aligned rows: the per-wave streaming kernel of csrc/rowgemm.hip
   if (hrow_supported(d, dtype, h, ldh, nullptr, 0, nullptr, 0, out, ldo) && reinterpret_cast<uintptr_t>(den) % 16 == 0)
@@ -1730,7 +1737,7 @@ extern "C" int sgf_attn_h_bwd_reduce(const void* h, int64_t ldh, const void* g, 
                                      const void* o, int64_t ldo, const float* den, int64_t n,
                                      int32_t d, int32_t dtype, float* hstats, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  int rc = check_common("sgf_attn_h_bwd_reduce", n, 1, d, dtype);
+  int rc = check_common_h("sgf_attn_h_bwd_reduce", n, d, dtype);
   if (rc != SGF_OK) return rc;
   SGF_REQUIRE(hstats, SGF_E_INVALID, "sgf_attn_h_bwd_reduce: null hstats");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1741,6 +1748,17 @@ extern "C" int sgf_attn_h_bwd_reduce(const void* h, int64_t ldh, const void* g, 
   SGF_REQUIRE(h && g && o && den, SGF_E_INVALID, "sgf_attn_h_bwd_reduce: null pointer");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_attn_workspace_bytes(n, 1, d), SGF_E_WORKSPACE,
               "sgf_attn_h_bwd_reduce: workspace too small");
+  if (dtype == SGF_F32_BF16X3) {
+    int nb = 0, DP = 0, RG = 0;
+    rc = attn_h_f32x_bwd_reduce(static_cast<const float*>(h), ldh, static_cast<const float*>(g), ldg,
+                                static_cast<const float*>(o), ldo, den, n, d, static_cast<float*>(workspace), &nb, &DP, &RG, st);
+    if (rc != SGF_OK) return rc;
+    const int64_t len = sgf_attn_h_bstats_len(d);
+    hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st,
+                       static_cast<const float*>(workspace), nb, d, DP, RG, hstats);
+    SGF_LAUNCH_CHECK();
+    return SGF_OK;
+  }
   if (dtype == SGF_F32)
     return h_bwd_reduce_t<float>(h, ldh, g, ldg, o, ldo, den, n, d, hstats, workspace, st);
   return h_bwd_reduce_t<uint16_t>(h, ldh, g, ldg, o, ldo, den, n, d, hstats, workspace, st);
@@ -1751,12 +1769,15 @@ extern "C" int sgf_attn_h_bwd_apply(const void* h, int64_t ldh, const void* g, i
                                     int32_t dtype, const float* M, const float* w, const float* D,
                                     const float* ds, void* dh, int64_t lddh, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-  int rc = check_common("sgf_attn_h_bwd_apply", n, 1, d, dtype);
+  int rc = check_common_h("sgf_attn_h_bwd_apply", n, d, dtype);
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(h && g && o && den && M && w && D && ds && dh, SGF_E_INVALID,
               "sgf_attn_h_bwd_apply: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == SGF_F32_BF16X3)
+    return attn_h_f32x_bwd_apply(static_cast<const float*>(h), ldh, static_cast<const float*>(g), ldg,
+                                 static_cast<const float*>(o), ldo, den, n, d, M, w, D, ds, static_cast<float*>(dh), lddh, st);
   if (dtype == SGF_F32)
     return h_bwd_apply_t<float>(h, ldh, g, ldg, o, ldo, den, n, d, M, w, D, ds, dh, lddh, st);
   if (hrow_supported(d, dtype, h, ldh, g, ldg, o, ldo, dh, lddh)) {
@@ -1771,6 +1792,13 @@ extern "C" int sgf_attn_h_bwd_apply(const void* h, int64_t ldh, const void* g, i
 extern "C" size_t sgf_attn_h_bwd_apply_workspace_bytes(int64_t n, int32_t d, int32_t dtype) {
   if (n <= 0 || dtype != SGF_BF16 || !(d == 64 || d == 128 || d == 256)) return 0;
   return hrow_partial_bytes(n, d);
+}
+
+// what each dtype code can run through sgf_attn_h_fwd / _bwd_reduce / _bwd_apply
+extern "C" int32_t sgf_attn_h_supported(int32_t d, int32_t dtype) {
+  if (d < 1 || d % 4 != 0 || d > 256) return 0;
+  if (dtype == SGF_F32_BF16X3) return attn_h_f32x_supported(d) ? 1 : 0;
+  return dtype == SGF_F32 || dtype == SGF_BF16 ? 1 : 0;
 }
 
 // ---- the same backward as three calls, so that the reduce can use the row scalars the first apply pass computes ----

@@ -30,6 +30,18 @@ bool gram_f32x_supported(const void* a, int64_t lda, int m, const void* b, int64
 int gram_f32x(const float* a, int64_t lda, int m, const float* b, int64_t ldb, int k, int64_t n, float* partial, int* nblk,
               hipStream_t st);
 
+// ---- csrc/attn_f32x.hip: the row passes of the attention from the un-projected input over fp32 storage as three bf16
+// products (SGF_F32_BF16X3); rows 16-byte aligned, d a multiple of 4 up to 256, n > 0.  The reduce leaves per-block partials
+// in the layout above (*DP, *RG: what k_hbwd_finalize of attn.hip has to be told)
+bool attn_h_f32x_supported(int d);
+int attn_h_f32x_fwd(const float* h, int64_t ldh, int64_t n, int d, const float* M, const float* m, const float* w,
+                    const float* beta, float* out, int64_t ldo, float* den, hipStream_t st);
+int attn_h_f32x_bwd_apply(const float* h, int64_t ldh, const float* g, int64_t ldg, const float* o, int64_t ldo,
+                          const float* den, int64_t n, int d, const float* M, const float* w, const float* D,
+                          const float* ds, float* dh, int64_t lddh, hipStream_t st);
+int attn_h_f32x_bwd_reduce(const float* h, int64_t ldh, const float* g, int64_t ldg, const float* o, int64_t ldo,
+                           const float* den, int64_t n, int d, float* partial, int* nblk, int* DP, int* RG, hipStream_t st);
+
 // the stems' dW / db with the A operand formed in LDS from the streamed tensors (k_gramt): BatchNorm / LayerNorm backward;
 // every tensor operand 16-byte aligned with ld % 8 == 0 (gramt_aligned), k <= 128.  LN: second / third vector = dbeta / dgamma
 bool gramt_supported(int m, int k, int64_t n);

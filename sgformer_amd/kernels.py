@@ -572,7 +572,7 @@ class HipKernels:
         out = torch.empty((n, d), dtype=h.dtype, device=dev)
         den = torch.empty((n, 1), dtype=_F32, device=dev)
         with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_fwd", _ptr(h), _ld(h), n, d, _code(h), _ptr(M), _ptr(m), _ptr(w),
+            _lib.call("sgf_attn_h_fwd", _ptr(h), _ld(h), n, d, _mm_code(h, "sgf_attn_h_supported", d), _ptr(M), _ptr(m), _ptr(w),
                       _ptr(beta), _ptr(out), out.stride(0), _ptr(den), _stream(dev))
         return out, den
 
@@ -585,7 +585,7 @@ class HipKernels:
         ws = _workspace(dev, "attn", lib.sgf_attn_workspace_bytes(n, 1, d))
         with torch.cuda.device(dev):
             _lib.call("sgf_attn_h_bwd_reduce", _ptr(h), _ld(h), _ptr(g), _ld(g), _ptr(o), _ld(o),
-                      _ptr(den), n, d, _code(h), _ptr(hstats), _ptr(ws), ws.numel(), _stream(dev))
+                      _ptr(den), n, d, _mm_code(h, "sgf_attn_h_supported", d), _ptr(hstats), _ptr(ws), ws.numel(), _stream(dev))
         return hstats
 
     @staticmethod
@@ -593,11 +593,12 @@ class HipKernels:
         n, d = h.shape
         dev = h.device
         dh = torch.empty((n, d), dtype=h.dtype, device=dev)
-        nb = _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, _code(h))
+        code = _mm_code(h, "sgf_attn_h_supported", d)
+        nb = _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, code)
         ws = _workspace(dev, "attn_h_part", nb) if nb else None
         with torch.cuda.device(dev):
             _lib.call("sgf_attn_h_bwd_apply", _ptr(h), _ld(h), _ptr(g), _ld(g), _ptr(o), _ld(o),
-                      _ptr(den), n, d, _code(h), _ptr(M), _ptr(w), _ptr(D), _ptr(ds), _ptr(dh),
+                      _ptr(den), n, d, code, _ptr(M), _ptr(w), _ptr(D), _ptr(ds), _ptr(dh),
                       dh.stride(0), _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev))
         return dh
 
