@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 630 /* 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 640 /* 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -905,6 +905,50 @@ int sgf_bce_fwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t d
 int sgf_bce_bwd(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* target,
                 int64_t ldt, int32_t target_kind, const int64_t* idx, int64_t m, const float* gout,
                 float inv_denom, void* dlogits, int64_t ldd, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N5 — the trainers' evaluation metrics.   Replaces large/data_utils.py:199-246 (the same functions in medium/ and 100M/):
+ *     eval_rocauc : per label column a device->host copy of [m] scores and labels and one scikit-learn roc_auc_score
+ *                   (a host sort) — 336 host sorts per evaluation of ogbn-proteins (112 columns, three splits)
+ *     eval_acc / eval_f1 : argmax, device->host copy, numpy compare
+ * Both entries return INTEGER counts on the device; the host finishes the metric with one division per column.  Every
+ * result is exact and bit-reproducible whatever the launch geometry.  No hidden allocation, no host sync.
+ *
+ * sgf_rocauc_counts : counts int64 [c, 6]; for column k, over the selected rows r_j = idx[j] (idx == NULL: rows 0..m-1,
+ *   m == n):
+ *     [0] P           rows with label == 1
+ *     [1] Nn          rows with label == 0
+ *     [2] U2          sum over positive i of ( 2 #{negative j : s_j < s_i} + #{negative j : s_j == s_i} )
+ *     [3] other       labelled rows whose label is neither 0 nor 1
+ *     [4] nan_scores  labelled rows whose score is NaN
+ *     [5] unlabelled  rows whose label is NaN (SGF_METRIC_TARGET_F32 only)
+ *   AUC_k = U2 / (2 P Nn): scikit-learn's trapezoid AUC with ties counted half (Mann-Whitney).  Rows counted under [3], [4]
+ *   or [5] do not enter P, Nn or U2 (a row can count under both [3] and [4]).  Scores compare as fp32 values: bf16 is
+ *   widened exactly, -0.0 == +0.0, +-inf are ordinary values.  m < 2^31 (so U2 < 2^62), c < 2^27.
+ *   logits [n, c] SGF_F32 or SGF_BF16, leading dim ldl; target [n, c] indexed by NODE id, leading dim ldt:
+ *     SGF_METRIC_TARGET_F32 : fp32 (NaN = unlabelled)        SGF_METRIC_TARGET_I64 : int64
+ *   idx int64 [m] rows in [0, n); an entry outside that range is not read and counts under [3] in every column.
+ *   Work: one key pass, one radix sort of m * c 64-bit keys (column in the top bits: a single long column is sorted by
+ *   the whole chip), one rank pass.  Workspace: sgf_rocauc_workspace_bytes(m, c) — two key buffers of 8 m c bytes
+ *   and the sort's temporary of about as much again, some 24 m c bytes in all (0: the size query failed, sgf_last_error() says why).
+ *
+ * sgf_argmax_count : counts int64 [2] = { labelled rows, rows whose argmax equals the label } over the selected rows, one
+ *   pass, no [m, c] copy and no [m] prediction tensor.  argmax as torch.argmax on the CPU: the first maximal column; a NaN
+ *   counts as the maximum and the first NaN wins.  labels: one per NODE, element r at labels[r * label_stride] (the
+ *   trainers keep [N, 1]); label_kind SGF_METRIC_TARGET_I64 (every row labelled) or SGF_METRIC_TARGET_F32 (NaN =
+ *   unlabelled; equal when float(argmax) == label).  An idx entry outside [0, n) is not read and not counted.
+ *   Per-block integer partials summed in a fixed order.  Workspace: sgf_argmax_workspace_bytes(m, c).
+ * ------------------------------------------------------------------------------------------ */
+#define SGF_METRIC_TARGET_F32 0
+#define SGF_METRIC_TARGET_I64 1
+size_t sgf_rocauc_workspace_bytes(int64_t m, int32_t c);
+int sgf_rocauc_counts(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* target,
+                      int64_t ldt, int32_t target_kind, const int64_t* idx, int64_t m, int64_t* counts,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t sgf_argmax_workspace_bytes(int64_t m, int32_t c);
+int sgf_argmax_count(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* labels,
+                     int64_t label_stride, int32_t label_kind, const int64_t* idx, int64_t m, int64_t* counts,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

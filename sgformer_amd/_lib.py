@@ -18,6 +18,8 @@ SGF_F32_BF16X3 = 2   # fp32 storage, matrix products as three bf16 products (inc
 SGF_BCE_TARGET_F32 = 0     # target kinds of sgf_bce_fwd / _bwd: fp32 [n, c]
 SGF_BCE_TARGET_I64 = 1     # int64 0 / 1 [n, c]
 SGF_BCE_TARGET_CLASS = 2   # int64 class indices [n]
+SGF_METRIC_TARGET_F32 = 0  # label kinds of sgf_rocauc_counts / sgf_argmax_count: fp32 (NaN = unlabelled)
+SGF_METRIC_TARGET_I64 = 1  # int64
 
 _lib = None
 
@@ -158,6 +160,12 @@ SIGNATURES = {
                               c_size_t, _P]),
     "sgf_bce_bwd": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, c_float, _P,
                               c_int64, _P]),
+    "sgf_rocauc_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "sgf_rocauc_counts": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P,
+                                    c_size_t, _P]),
+    "sgf_argmax_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "sgf_argmax_count": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P,
+                                   c_size_t, _P]),
     "sgf_sum_n": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64, _P]),
     "sgf_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_colsum": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P]),

@@ -960,6 +960,81 @@ class HipKernels:
                 _lib.call("sgf_bce_bwd", *args)
         return d
 
+    # ---- N5: the evaluation metrics as integer counts (idx None: every row) ----
+    @staticmethod
+    def _metric_args(what, logits, labels, idx, per_column: bool):
+        """(n, c, m, labels, kind, label stride) after the checks both entries share: logits [n, c] fp32 / bf16 with unit inner
+        stride and rows that do not overlap; labels fp32 or int64, [n, c] with contiguous rows (per_column) or one per node
+        as [n] / [n, 1] with any stride; idx int64 [m] contiguous or None."""
+        if logits.dim() != 2 or logits.stride(1) != 1 or (logits.stride(0) < logits.shape[1] and logits.shape[0] > 1):
+            raise ValueError(f"{what}: logits must be [n, c] with unit inner stride and a row stride >= c, got shape "
+                             f"{tuple(logits.shape)} strides {logits.stride()}")
+        n, c = logits.shape
+        if c < 1:
+            raise ValueError(f"{what}: logits need at least one column, got shape {tuple(logits.shape)}")
+        if labels.device != logits.device or (idx is not None and idx.device != logits.device):
+            raise ValueError(f"{what}: logits, labels and idx must be on the same device")
+        if labels.dtype == _F32:
+            kind = _lib.SGF_METRIC_TARGET_F32
+        elif labels.dtype == torch.int64:
+            kind = _lib.SGF_METRIC_TARGET_I64
+        else:
+            raise ValueError(f"{what}: labels must be float32 or int64, got {labels.dtype}")
+        if per_column:
+            if labels.dim() != 2 or labels.shape != logits.shape:
+                raise ValueError(f"{what}: labels must be {tuple(logits.shape)}, got {tuple(labels.shape)}")
+            if labels.stride(1) != 1 or (labels.stride(0) < c and n > 1):
+                raise ValueError(f"{what}: label rows must be contiguous, got strides {labels.stride()}")
+            stride = max(labels.stride(0), c)
+        else:
+            if labels.shape not in ((n,), (n, 1)):
+                raise ValueError(f"{what}: labels must be [{n}] or [{n}, 1], got {tuple(labels.shape)}")
+            stride = max(labels.stride(0), 1)
+            if n > 1 and labels.stride(0) < 1:
+                raise ValueError(f"{what}: labels must have a positive stride, got {labels.stride()}")
+        if idx is None:
+            m = n
+        else:
+            if idx.dim() != 1 or idx.dtype != torch.int64 or not idx.is_contiguous():
+                raise ValueError(f"{what}: idx must be a contiguous int64 vector, got {idx.dtype} {tuple(idx.shape)}")
+            m = idx.numel()
+        if m >= 2 ** 31:
+            raise ValueError(f"{what}: {m} rows, the limit is 2^31 - 1")
+        return n, c, m, labels, kind, stride
+
+    @staticmethod
+    def rocauc_counts(logits, target, idx) -> torch.Tensor:
+        """int64 [c, 6] on the device: per column P, Nn, U2, other, nan_scores, unlabelled (include/sgf.h block N5)."""
+        n, c, m, target, kind, ldt = HipKernels._metric_args("rocauc_counts", logits, target, idx, True)
+        dev = logits.device
+        counts = torch.empty((c, 6), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            nbytes = int(_lib.load().sgf_rocauc_workspace_bytes(m, c)) if m else 0
+            if m and c >= 1 and nbytes == 0:
+                _lib.check(_lib.SGF_E_HIP if hasattr(_lib, "SGF_E_HIP") else -3, "sgf_rocauc_workspace_bytes")
+            # some 24 m c bytes (230 MB at the ogbn-proteins train split) for a call made once every eval_step epochs:
+            # taken from the caching allocator and given back, not kept in the per-stream scratch cache
+            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+            _lib.call("sgf_rocauc_counts", _ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(target), ldt, kind,
+                      _ptr(idx), m, _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+        return counts
+
+    _argmax_ws_bytes = None
+
+    @staticmethod
+    def argmax_count(logits, labels, idx) -> torch.Tensor:
+        """int64 [2] on the device: { labelled rows, rows whose argmax equals the label } (include/sgf.h block N5)."""
+        n, c, m, labels, kind, stride = HipKernels._metric_args("argmax_count", logits, labels, idx, False)
+        dev = logits.device
+        counts = torch.empty((2,), dtype=torch.int64, device=dev)
+        if HipKernels._argmax_ws_bytes is None:    # (a constant of the library: the block-partial buffer)
+            HipKernels._argmax_ws_bytes = int(_lib.load().sgf_argmax_workspace_bytes(m, c))
+        with torch.cuda.device(dev):
+            ws = _workspace(dev, "argmax", HipKernels._argmax_ws_bytes)
+            _lib.call("sgf_argmax_count", _ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(labels), stride,
+                      kind, _ptr(idx), m, _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+        return counts
+
     @staticmethod
     def sum_n(xs) -> torch.Tensor:
         """sum of up to 8 equally shaped [n, d] tensors in one pass."""

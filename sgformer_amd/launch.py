@@ -34,6 +34,9 @@ cover; tests/test_launch_patches.py drives each with callers that are not the re
     torch_geometric.utils.to_undirected / remove_self_loops / add_self_loops                    --sgf-host-prologue 1
     torch_geometric.loader.NeighborLoader (100M only)                                           --sgf-host-sampler 1
     dataset.load_dataset (node features resident on the GPU, main-batch.py only)                --sgf-host-features 1
+    data_utils.eval_acc / eval_rocauc / eval_f1 (the TRAINER's own module)                      --sgf-host-metrics 1
+                                        integer counts from the device, one host read per call, from the
+                                        measured size on (launch.EVAL_PATCH_MIN_ROWS; --sgf-device-metrics 1: always)
     torch.set_num_threads(4)  (main-batch.py only)                                              OMP_NUM_THREADS=...
 
     --sgf-patches minimal  (or SGF_PATCHES=minimal)   none of the above: the module drop-in only.
@@ -295,6 +298,55 @@ def unpatch_bce_loss():
         F.binary_cross_entropy_with_logits = orig
 
 
+# Rows from which each drop-in metric takes a call; below it — and always where the entry is None — the call goes to the
+# trainer's own function, so a patched trainer is never slower than an unpatched one.  A number here is a crossover
+# MEASURED by scripts/metrics_probe.py (profiles/metrics_probe.md: the original against the drop-in on host tensors, the
+# form evaluate_large uses): the smallest probed row count at which the drop-in was ahead — eval_acc lost at 1 000 rows
+# (0.02 ms against 0.09 ms) and won at 90 941; None would mean no measurement says the drop-in wins.  `--sgf-device-metrics 1` takes every size.
+EVAL_PATCH_MIN_ROWS = {"eval_acc": 90941, "eval_rocauc": 2000, "eval_f1": 1000}
+EVAL_NAMES = ("eval_acc", "eval_rocauc", "eval_f1")
+
+
+def patch_eval_metrics(min_rows=None):
+    """The trainers take their metric from their own data_utils (`from data_utils import eval_acc, eval_rocauc, eval_f1`,
+    large/main.py; large/data_utils.py:199-246): an argmax, a device->host copy and a numpy compare, or — eval_rocauc — one
+    scikit-learn roc_auc_score (a host sort) per label column, 336 per evaluation of ogbn-proteins.  Import the trainer's
+    own data_utils (its directory is on sys.path by now, as for patch_100m_data_utils) and bind the three names to
+    sgformer_amd.metrics' drop-ins before the trainer imports them: integer counts formed on the device
+    (sgf_rocauc_counts / sgf_argmax_count), one host read per call, the same return values.  Each drop-in keeps the
+    original and calls it for anything it does not cover and for fewer than `min_rows` rows (default: per function,
+    EVAL_PATCH_MIN_ROWS, where None sends every call to the original; an int here applies to all three).
+    `--sgf-host-metrics 1` keeps the trainer's functions, `--sgf-device-metrics 1` is min_rows = 0.  Idempotent; returns the module, or None
+    when the trainer has no data_utils."""
+    import importlib as _il
+    from . import metrics
+    try:
+        du = _il.import_module("data_utils")
+    except ModuleNotFoundError:
+        return None
+    for name in EVAL_NAMES:
+        least = EVAL_PATCH_MIN_ROWS[name] if min_rows is None else int(min_rows)
+        least = float("inf") if least is None else least
+        fn = getattr(du, name, None)
+        if fn is None:
+            continue
+        orig = getattr(fn, "_sgf_orig", fn)
+        new = metrics.MAKERS[name](orig, least)
+        new._sgf_orig = orig
+        setattr(du, name, new)
+    return du
+
+
+def unpatch_eval_metrics():
+    du = sys.modules.get("data_utils")
+    if du is None:
+        return
+    for name in EVAL_NAMES:
+        orig = getattr(getattr(du, name, None), "_sgf_orig", None)
+        if orig is not None:
+            setattr(du, name, orig)
+
+
 def patch_adam():
     """torch.optim.Adam as the trainers construct it (large/main.py:114-119: two parameter groups, no `fused` / `foreach`
     argument) runs its for-each form: ~12 multi-tensor launches per group and step.  For CUDA parameters torch's own
@@ -398,6 +450,8 @@ def main(argv=None):
     host_features = _pop_option(argv, "--sgf-host-features")   # any value: keep node features on the host
     aten_loss = _pop_option(argv, "--sgf-aten-loss")           # any value: keep ATen's nll_loss and BCE kernels
     host_sampler = _pop_option(argv, "--sgf-host-sampler")     # any value: keep PyG's host NeighborLoader (100M)
+    host_metrics = _pop_option(argv, "--sgf-host-metrics")     # any value: keep the trainer's own eval_acc / _rocauc / _f1
+    device_metrics = _pop_option(argv, "--sgf-device-metrics")  # any value: the drop-in metrics at every size
     patches = _pop_option(argv, "--sgf-patches") or os.environ.get("SGF_PATCHES", "all")
     if patches not in ("all", "minimal"):
         raise SystemExit(f"sgformer_amd.launch: --sgf-patches {patches!r} (choose 'all' or 'minimal')")
@@ -426,7 +480,8 @@ def main(argv=None):
     if patches == "minimal":
         # the module drop-in ONLY: `ours` (and, for the medium / 100M trainers, the two repairs above, which touch the
         # TRAINER's own modules) — nothing of torch, torch_geometric or the host thread pool is rewired: F.log_softmax,
-        # F.nll_loss, F.binary_cross_entropy_with_logits, torch.optim.Adam, torch_geometric.utils.* and NeighborLoader stay what the environment provides
+        # F.nll_loss, F.binary_cross_entropy_with_logits, torch.optim.Adam, torch_geometric.utils.* and NeighborLoader stay what the environment provides,
+        # and the trainer's eval_acc / eval_rocauc / eval_f1 stay its own
         runpy.run_path(trainer, run_name="__main__")
         return
     if host_subgraph is None and os.path.basename(trainer) == "main-batch.py":
@@ -441,6 +496,8 @@ def main(argv=None):
         patch_nll_loss()
         patch_bce_loss()
     patch_adam()
+    if host_metrics is None:
+        patch_eval_metrics(0 if device_metrics is not None else None)
     if os.path.basename(trainer) == "main-batch.py":
         limit_host_threads()
         if host_features is None:

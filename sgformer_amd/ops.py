@@ -521,6 +521,44 @@ def bce_loss_rows(logits, target, idx, denom=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# N5: the evaluation metrics as integer counts (large/data_utils.py:199-246).  No autograd: a metric has no gradient.
+# ------------------------------------------------------------------------------------------------
+def _no_grad_inputs(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"sgformer_amd: {what} is not differentiable; detach its inputs or call it under torch.no_grad()")
+
+
+def _metric_idx(idx):
+    if idx is not None and idx.dtype == torch.bool:
+        return idx.nonzero().view(-1)
+    return None if idx is None else idx.contiguous()
+
+
+def rocauc_counts(logits, target, idx=None) -> torch.Tensor:
+    """int64 [C, 6] on the logits' device: per label column P, Nn, U2, other, nan_scores, unlabelled over the rows `idx`
+    (int64 rows, a bool mask over N, or None for every row); AUC_k = U2 / (2 P Nn) (include/sgf.h block N5).  `target`:
+    [N, C] float32 (NaN = unlabelled) or int64, indexed by NODE id."""
+    _no_grad_inputs("rocauc_counts", logits, target)
+    K.check(logits, target, idx)
+    if logits.dim() == 2 and (logits.stride(1) != 1 or (logits.stride(0) < logits.shape[1] and logits.shape[0] > 1)):
+        logits = logits.contiguous()
+    if target.dim() == 2 and (target.stride(1) != 1 or (target.stride(0) < target.shape[1] and target.shape[0] > 1)):
+        target = target.contiguous()
+    return K.rocauc_counts(logits.detach(), target.detach(), _metric_idx(idx))
+
+
+def argmax_count(logits, labels, idx=None) -> torch.Tensor:
+    """int64 [2] on the logits' device: { labelled rows, rows whose argmax equals the label } over the rows `idx`.  `labels`:
+    [N] or [N, 1] (any stride) int64, or float32 with NaN = unlabelled, indexed by NODE id.  argmax as torch.argmax on the
+    CPU: first maximal column, NaN counts as the maximum (include/sgf.h block N5)."""
+    _no_grad_inputs("argmax_count", logits, labels)
+    K.check(logits, labels, idx)
+    if logits.dim() == 2 and (logits.stride(1) != 1 or (logits.stride(0) < logits.shape[1] and logits.shape[0] > 1)):
+        logits = logits.contiguous()
+    return K.argmax_count(logits.detach(), labels.detach(), _metric_idx(idx))
+
+
+# ------------------------------------------------------------------------------------------------
 # row permutation at the module boundary (re-ordered graphs) and mini-batch row gathers
 # ------------------------------------------------------------------------------------------------
 class _PermuteRows(torch.autograd.Function):
