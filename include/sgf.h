@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 640 /* 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 650 /* 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -359,6 +359,54 @@ int sgf_neighbor_sample_batch(const int64_t* rowptr, const int32_t* colind, cons
                               const int32_t* fanouts, int32_t hops, uint64_t seed, uint64_t batch, int32_t* local_of,
                               int32_t* nodes, int64_t node_cap, int32_t* edge_src_local, int32_t* edge_dst_local,
                               int64_t edge_cap, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N2 + T1 — the normalised CSR of a neighbour-sampled batch, and its transpose, from what the sampler emits
+ * (csrc/sampled_csr.hip).   Replaces 100M/ours.py:72-79 (= large/ours.py:26-33) for the batch — the degree + argsort every
+ * GraphConvLayer.forward redoes — and, for the transpose, large/ours.py:34 under autograd (torch_sparse transposes the
+ * adjacency in the backward of matmul).  sgf_csr_build / sgf_csr_transpose do the same for ANY edge list with two radix sorts
+ * of 64-bit keys and a symmetry flag read on the host; a sampled batch needs neither.
+ *
+ * sgf_sampled_csr_build (100M/ours.py:72-79 = large/ours.py:26-33): runs BEFORE the batch's one host read.
+ *   edge_src_local / edge_dst_local : int32 [edge_cap], what sgf_neighbor_sample_batch wrote
+ *   counts     : the device array sgf_neighbor_sample_batch wrote; counts[0] = nn (nodes), counts[1] = ne (edges), read on
+ *                the device — launches are sized by node_cap / edge_cap
+ *   rowptr_b   : int64 [node_cap + 1], colind_b int32 [edge_cap], val_b fp32 [edge_cap], deg_b int32 [node_cap + 1]   out
+ * Contract: rowptr_b[:nn + 1], colind_b[:ne], val_b[:ne], deg_b[:nn] == bit for bit what sgf_csr_build returns for the edge
+ * list (edge_src_local[:ne], edge_dst_local[:ne]) with n = nn: entries ordered by (target, source), duplicates kept,
+ * val = the IEEE fp32 product of two correctly rounded sqrtf(1.0f / deg) terms, non-finite -> 0 (the nodes that entered in the
+ * last hop have in-degree 0).  Nothing is written behind those prefixes.
+ * Precondition (what the sampler guarantees: edges hop after hop, frontier order inside a hop, every node a frontier node
+ * once): edge_dst_local[:ne] is non-decreasing and no row is longer than max_fanout.  rowptr is then a lower bound into
+ * edge_dst_local and a row is ordered by ranking its <= max_fanout sources.  Entries that break the precondition are dropped,
+ * never written out of bounds.
+ * sgf_sampled_csr_supported(max_fanout): 1 for 0 <= max_fanout <= 256 (a row is ranked in O(len^2)), else 0 — there
+ * sgf_sampled_csr_build returns SGF_E_UNSUPPORTED and the caller keeps sgf_csr_build.  Inside the kernels max_fanout is
+ * advisory: a row longer than it is still ordered correctly, only in more time.
+ * No radix sort, no atomics, no host synchronisation, no hidden allocation (the workspace query returns 0: `workspace` may
+ * be NULL); deterministic whatever the launch geometry.
+ *
+ * sgf_sampled_csr_transpose (large/ours.py:34 under autograd: dX = A^T dY): host-known n / nnz, called lazily at the first
+ * backward, for any CSR whose rows are in ascending source order.
+ *   t_rowptr int64 [n + 1], t_colind int32 [nnz], t_val fp32 [nnz] == bit for bit the t_rowptr / t_colind / t_val of
+ *   sgf_csr_transpose for the same graph: entries ordered by (source, target), the value that of the forward entry.
+ * A stable sort of (source, forward entry number) pairs by the ceil(log2 n) significant bits of the 32-bit source (rocPRIM
+ * LSD radix sort: a counting sort per digit) — forward entries are already in target order, so stability IS the order
+ * inside a transposed row, however long that row is; t_rowptr = lower bounds into the sorted sources.  No 64-bit keys, no
+ * atomics in the library's own kernels (rocPRIM's sort counts digits with integer atomics; it is stable, so the result is
+ * deterministic), no symmetry test and no host read: the caller treats the batch graph as not symmetric (if it happens to
+ * be, the transposed arrays equal the forward ones).  A workspace too small for the two entry arrays (8 bytes per entry) is
+ * refused before any HIP call; the exact size check follows rocPRIM's size query.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_sampled_csr_supported(int32_t max_fanout);
+size_t sgf_sampled_csr_build_workspace_bytes(int64_t node_cap, int64_t edge_cap);
+int sgf_sampled_csr_build(const int32_t* edge_src_local, const int32_t* edge_dst_local, const int64_t* counts,
+                          int64_t node_cap, int64_t edge_cap, int32_t max_fanout, int64_t* rowptr_b, int32_t* colind_b,
+                          float* val_b, int32_t* deg_b, void* workspace, size_t workspace_bytes, void* stream);
+size_t sgf_sampled_csr_transpose_workspace_bytes(int64_t n, int64_t nnz);
+int sgf_sampled_csr_transpose(const int64_t* rowptr, const int32_t* colind, const float* val, int64_t n, int64_t nnz,
+                              int64_t* t_rowptr, int32_t* t_colind, float* t_val, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* dst[i, :] = src[idx[i], :] with an optional fp32 <-> bf16 storage change.  Replaces the row
  * gathers at the module boundary: x[idx_i] of a mini-batch (large/main-batch.py:138) and the

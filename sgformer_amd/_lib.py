@@ -76,6 +76,11 @@ SIGNATURES = {
                                             c_int64, _P, _P, c_size_t, _P]),
     "sgf_neighbor_sample_hop": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_uint64, c_uint64, c_int32, _P, c_int32,
                                           c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sgf_sampled_csr_supported": (c_int32, [c_int32]),
+    "sgf_sampled_csr_build_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sgf_sampled_csr_build": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sgf_sampled_csr_transpose_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "sgf_sampled_csr_transpose": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
     "sgf_gather_rows": (c_int32, [_P, c_int64, c_int32, c_int64, _P, c_int32, c_int64, c_int32, _P, c_int64,
                                   c_int32, _P]),
     "sgf_pad_rows": (c_int32, [_P, c_int64, c_int32, c_int64, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64,

@@ -78,6 +78,9 @@ class CSRGraph:
             # the producer of this edge list (batching.subgraph on the parent's CSR: sgf_subgraph_csr_*) built the normalised
             # CSR in the same pass — bit for bit what sgf_csr_build would return for it (tests/test_gpu_r05.py)
             self.rowptr, self.colind, self.val, self.deg = pre
+            # a neighbour-sampled batch (sampling.NeighborSampler: sgf_sampled_csr_build): directed, its rows in ascending
+            # source order — transposed() takes sgf_sampled_csr_transpose
+            self._t_lazy = bool(getattr(edge_index, "_sgf_csr_t_lazy", False))
         else:
             self.rowptr, self.colind, self.val, self.deg = K.csr_build(ei, n)
         # longest possible row: only a bound the caller GUARANTEES (sampling.NeighborSampler marks its batches with their
@@ -96,6 +99,12 @@ class CSRGraph:
 
     def transposed(self):
         """CSR of A^T for dX = A^T dY; the same arrays when A is symmetric."""
+        if self._t is None and self._t_lazy:
+            # no second sort of the edge list, no comparison pass, no host read in the middle of the backward: `symmetric` is
+            # set without looking (were the batch graph symmetric, these arrays would equal the forward ones)
+            self._t = K.sampled_csr_transpose(self.rowptr, self.colind, self.val, self.n)
+            self.symmetric = False
+            self.t_long_segments = long_row_segments(self._t[0], self.nnz)
         if self._t is None:
             t_rowptr, t_colind, t_val, sym = K.csr_transpose(self.edge_index, self.n, self.deg,
                                                              self.rowptr, self.colind)
@@ -106,6 +115,7 @@ class CSRGraph:
 
     # ---- LDS-staged row-block SpMM: one plan per (orientation, storage dtype) ----
     blocked = False          # set by GraphView when the plan serves enough entries from LDS
+    _t_lazy = False          # set when the edge list came with a sampled batch's CSR (sgf_sampled_csr_*)
 
     def plan(self, dtype, transposed: bool = False):
         """BlockedPlan for SpMMs with `dtype` storage on this CSR (or its transpose), or None."""

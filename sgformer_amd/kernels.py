@@ -242,6 +242,42 @@ class HipKernels:
             return None
         return rowptr_b, colind_b, val_b, deg_b[:m], ei_b, int(longest)
 
+    # ---- N2 + T1: the CSR of a neighbour-sampled batch and its transpose (csrc/sampled_csr.hip) ----
+    @staticmethod
+    def sampled_csr_supported(max_fanout: int) -> bool:
+        return bool(_lib.load().sgf_sampled_csr_supported(int(max_fanout)))
+
+    @staticmethod
+    def sampled_csr_build(e_src: torch.Tensor, e_dst: torch.Tensor, counts: torch.Tensor, node_cap: int, edge_cap: int,
+                          max_fanout: int):
+        """Capacity-sized (rowptr_b [node_cap + 1], colind_b [edge_cap], val_b [edge_cap], deg_b [node_cap + 1]) of the batch
+        sgf_neighbor_sample_batch left in e_src / e_dst / counts (all on the device: no host read here).  The caller slices
+        the prefixes [:nn + 1], [:ne], [:ne], [:nn] once it has read the counts: those equal csr_build's arrays bit for bit."""
+        dev = e_src.device
+        rowptr_b = torch.empty(node_cap + 1, dtype=torch.int64, device=dev)
+        colind_b = torch.empty(max(edge_cap, 1), dtype=torch.int32, device=dev)
+        val_b = torch.empty(max(edge_cap, 1), dtype=_F32, device=dev)
+        deg_b = torch.empty(node_cap + 1, dtype=torch.int32, device=dev)
+        ws = _workspace(dev, "sampled_csr_build", _lib.load().sgf_sampled_csr_build_workspace_bytes(node_cap, edge_cap))
+        with torch.cuda.device(dev):
+            _lib.call("sgf_sampled_csr_build", _ptr(e_src), _ptr(e_dst), _ptr(counts), node_cap, edge_cap, int(max_fanout),
+                      _ptr(rowptr_b), _ptr(colind_b), _ptr(val_b), _ptr(deg_b), _ptr(ws), ws.numel(), _stream(dev))
+        return rowptr_b, colind_b, val_b, deg_b
+
+    @staticmethod
+    def sampled_csr_transpose(rowptr, colind, val, n: int):
+        """(t_rowptr, t_colind, t_val) of a CSR whose rows are in ascending source order — csr_transpose's arrays bit for bit,
+        without its symmetry flag: no host read."""
+        dev, nnz = rowptr.device, int(colind.numel())
+        t_rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        t_colind = torch.empty(nnz, dtype=torch.int32, device=dev)
+        t_val = torch.empty(nnz, dtype=_F32, device=dev)
+        ws = _workspace(dev, "sampled_csr_transpose", _lib.load().sgf_sampled_csr_transpose_workspace_bytes(n, nnz))
+        with torch.cuda.device(dev):
+            _lib.call("sgf_sampled_csr_transpose", _ptr(rowptr), _ptr(colind), _ptr(val), n, nnz, _ptr(t_rowptr), _ptr(t_colind),
+                      _ptr(t_val), _ptr(ws), ws.numel(), _stream(dev))
+        return t_rowptr, t_colind, t_val
+
     # ---- N2: trainer prologue (to_undirected / remove_self_loops / add_self_loops) ----
     @staticmethod
     def graph_prologue(ei: torch.Tensor, n: int, undirected: bool, remove_loops: bool, add_loops: bool):

@@ -40,9 +40,11 @@ class SampledBatch:
         mv = lambda t: t if (t is None or t.device == dev) else t.to(dev)   # noqa: E731
         out = SampledBatch(mv(self.x), mv(self.edge_index), mv(self.y), self.batch_size, mv(self.n_id))
         if out.edge_index is not self.edge_index:
-            for attr in ("_sgf_trusted", "_sgf_max_in_degree"):       # what ops.CSRGraph reads off a sampled edge list
+            # what ops.CSRGraph reads off a sampled edge list (the batch's CSR moves with it)
+            for attr in ("_sgf_trusted", "_sgf_max_in_degree", "_sgf_csr", "_sgf_csr_t_lazy"):
                 if hasattr(self.edge_index, attr):
-                    setattr(out.edge_index, attr, getattr(self.edge_index, attr))
+                    v = getattr(self.edge_index, attr)
+                    setattr(out.edge_index, attr, tuple(mv(t) for t in v) if attr == "_sgf_csr" else v)
         return out
 
 
@@ -75,6 +77,19 @@ def _shared_get(kind: str, key_tensors, extra, build):
             _shared.pop(next(iter(_shared)))
         hit = _shared[key] = (build(), key_tensors)
     return hit[0]
+
+
+# SGF_SAMPLED_CSR when the variable is not set: what scripts/sampled_csr_probe.py measured (profiles/sampled_csr_probe.md) —
+# the new entries are ahead of sgf_csr_build + sgf_csr_transpose by more than the run-to-run spread on both fan-out lists.
+SAMPLED_CSR_DEFAULT = "1"
+
+
+def _sampled_csr() -> bool:
+    """SGF_SAMPLED_CSR=0: a sampled batch carries its edge list only and ops.CSRGraph sorts it (sgf_csr_build, and
+    sgf_csr_transpose with its host read in the first backward), as before sgf_sampled_csr_*; any other value: the batch
+    comes with the CSR sgf_sampled_csr_build made."""
+    import os
+    return os.environ.get("SGF_SAMPLED_CSR", SAMPLED_CSR_DEFAULT) != "0"
 
 
 # above this worst-case entry count a batch is sampled hop by hop (buffers sized from the real frontier) instead of in one call
@@ -165,11 +180,20 @@ class NeighborSampler:
             except BaseException:
                 self.local_of.fill_(torch.iinfo(torch.int32).min)
                 raise
+        # the batch's normalised CSR from the edges as they were emitted (targets already in order, rows of at most
+        # max(fanouts) entries: sgf_sampled_csr_build) — queued BEFORE the host read, sized by the capacities
+        csr = None
+        if _sampled_csr() and ops.K.sampled_csr_supported(max(self.fanouts)):
+            csr = ops.K.sampled_csr_build(e_src, e_dst, counts, ncap, ecap, max(self.fanouts))
         nn, ne = (int(v) for v in counts[:2].tolist())          # the one host read of the batch
         self.host_reads += 1
         ei = torch.stack([e_src[:ne], e_dst[:ne]]).long()
         ei._sgf_trusted = True
         ei._sgf_max_in_degree = max(self.fanouts)       # every node is a frontier node once: at most fan-out in-edges
+        if csr is not None:
+            rowptr_b, colind_b, val_b, deg_b = csr
+            ei._sgf_csr = (rowptr_b[:nn + 1], colind_b[:ne], val_b[:ne], deg_b[:nn])     # ops.CSRGraph adopts these
+            ei._sgf_csr_t_lazy = True       # ... and transposes them with sgf_sampled_csr_transpose (no symmetry test, no host read)
         return nodes[:nn].long(), ei, bs
 
     def _hops(self, st, nodes, srcs, dsts, frontier, local0, n_known, batch_id):
