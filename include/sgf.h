@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 650 /* 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 660 /* 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -895,6 +895,14 @@ int sgf_axpby(const void* x1, int64_t ld1, float a, const void* x2, int64_t ld2,
  * ------------------------------------------------------------------------------------------ */
 int sgf_dropout(const void* x, int64_t ldx, const void* res, int64_t ldr, float p, uint64_t seed,
                 int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy, void* stream);
+
+/* sgf_dropout with the seed in DEVICE memory: the kernel reads all 64 bits of *seed_slot when it RUNS (each thread once,
+ * ahead of its loop), so a launch captured into a hipGraph draws a new mask on every replay once the slot has been
+ * rewritten on the same stream.  For the same seed value the output is bit-identical to sgf_dropout's.  seed_slot:
+ * non-null and 8-byte aligned when n > 0 (else SGF_E_INVALID); not read when n == 0. */
+int sgf_dropout_dev(const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
+                    const uint64_t* seed_slot, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * N4 — the trainer's loss.   Replaces large/main.py:139-141

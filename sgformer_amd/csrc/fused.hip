@@ -1009,11 +1009,21 @@ __device__ __forceinline__ uint32_t dropout_keep4(uint64_t seed, uint64_t chunk,
 }
 
 // y = x * keep / (1 - p) [+ res];  MODE 1 (backward): y = x * keep / (1 - p) with x = dL/dy
-template <typename T>
+// kDevSeed: `seed` carries the device address of the 64-bit seed (sgf_dropout_dev), read once per thread when the kernel
+// RUNS — a launch captured into a hipGraph draws a new mask on every replay once the host has rewritten the slot.  The
+// address is the same for every lane: one scalar load ahead of the loop, the streaming body is the immediate-seed one.
+template <typename T, bool kDevSeed>
 __global__ __launch_bounds__(kThreads) void k_dropout(const T* __restrict__ x, int64_t ldx,
                                                       const T* __restrict__ res, int64_t ldr, float p,
                                                       float scale, uint64_t seed, int64_t n, int d,
                                                       T* __restrict__ y, int64_t ldy) {
+  if (kDevSeed) {
+    // (made wave-uniform by hand: the ten round keys then stay in scalar registers as with the immediate seed — left as a
+    //  per-lane value the compiler keeps all twenty of them in vector registers, 56 instead of 22)
+    const uint64_t s = *reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(seed));
+    seed = static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s)))) |
+           (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s >> 32)))) << 32);
+  }
   const int f4 = d / 4;
   const int64_t total = n * f4;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < total;
@@ -1763,27 +1773,44 @@ extern "C" int sgf_sum_n(const void* const* xs, const int64_t* lds, int32_t k, i
   return SGF_OK;
 }
 
-extern "C" int sgf_dropout(const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
-                           uint64_t seed, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
-                           void* stream) {
-  int rc = check_ew("sgf_dropout", n, d, dtype);
+// sgf_dropout and sgf_dropout_dev: `seed` is the seed itself, or (kDevSeed) the device address it is read from
+template <bool kDevSeed>
+static int dropout_launch(const char* who, const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
+                          uint64_t seed, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy, void* stream) {
+  int rc = check_ew(who, n, d, dtype);
   if (rc != SGF_OK) return rc;
-  SGF_REQUIRE(p >= 0.f && p <= 1.f, SGF_E_INVALID, "sgf_dropout: p must be in [0, 1] (p=%f)", p);
+  SGF_REQUIRE(p >= 0.f && p <= 1.f, SGF_E_INVALID, "%s: p must be in [0, 1] (p=%f)", who, p);
   if (n == 0) return SGF_OK;
   SGF_REQUIRE(x && y && ldx % 4 == 0 && ldy % 4 == 0 && (!res || ldr % 4 == 0), SGF_E_INVALID,
-              "sgf_dropout: bad pointer / ld");
+              "%s: bad pointer / ld", who);
+  SGF_REQUIRE(!kDevSeed || (seed != 0 && seed % 8 == 0), SGF_E_INVALID,
+              "%s: seed_slot must be a non-null, 8-byte aligned device address", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
   const dim3 grid(ew_grid(n * (d / 4)));
   if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_dropout<float>), grid, dim3(kThreads), 0, st, static_cast<const float*>(x), ldx,
+    hipLaunchKernelGGL((k_dropout<float, kDevSeed>), grid, dim3(kThreads), 0, st, static_cast<const float*>(x), ldx,
                        static_cast<const float*>(res), ldr, p, scale, seed, n, d, static_cast<float*>(y), ldy);
   else
-    hipLaunchKernelGGL((k_dropout<uint16_t>), grid, dim3(kThreads), 0, st, static_cast<const uint16_t*>(x),
-                       ldx, static_cast<const uint16_t*>(res), ldr, p, scale, seed, n, d,
-                       static_cast<uint16_t*>(y), ldy);
+    hipLaunchKernelGGL((k_dropout<uint16_t, kDevSeed>), grid, dim3(kThreads), 0, st,
+                       static_cast<const uint16_t*>(x), ldx, static_cast<const uint16_t*>(res), ldr, p, scale, seed,
+                       n, d, static_cast<uint16_t*>(y), ldy);
   SGF_LAUNCH_CHECK();
   return SGF_OK;
+}
+
+extern "C" int sgf_dropout(const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
+                           uint64_t seed, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
+                           void* stream) {
+  return dropout_launch<false>("sgf_dropout", x, ldx, res, ldr, p, seed, n, d, dtype, y, ldy, stream);
+}
+
+extern "C" int sgf_dropout_dev(const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
+                               const uint64_t* seed_slot, int64_t n, int32_t d, int32_t dtype, void* y,
+                               int64_t ldy, void* stream) {
+  return dropout_launch<true>("sgf_dropout_dev", x, ldx, res, ldr, p,
+                              static_cast<uint64_t>(reinterpret_cast<uintptr_t>(seed_slot)), n, d, dtype, y, ldy,
+                              stream);
 }
 
 extern "C" size_t sgf_nll_workspace_bytes(int64_t m) {

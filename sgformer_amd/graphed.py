@@ -12,10 +12,25 @@ exactly as the eager path issues them) and replayed for every later batch of tha
     arrays (`StaticCSR`) the captured kernels read; the SpMM kernels bound their work by rowptr, so the stale tail of
     colind / val beyond the batch's nnz is never touched;
   * same arithmetic, same kernels, same order as the eager step: results are bit-identical (tests/test_gpu_graphed.py);
-  * engaged only where a replay is known to be equivalent: training mode with autograd, no active dropout (its Philox
-    offset is a launch argument), one GPU, a symmetric batch graph (batching.subgraph's promise for a symmetric parent: the
-    backward multiplies with the same arrays), features that do not require a gradient.  Everything else — evaluation, the
-    first batch of a size (it warms the caches the capture must not contain), odd shapes — runs the eager path;
+  * engaged only where a replay is known to be equivalent: training mode with autograd, one GPU, a symmetric batch graph
+    (batching.subgraph's promise for a symmetric parent: the backward multiplies with the same arrays), features that do
+    not require a gradient, and dropout either inactive or served by the fused kernel at every active site (hidden width a
+    multiple of 4, ours._drop: ATen's F.dropout has a generator of its own and stays a reason to run eager).  Everything
+    else — evaluation, the first batch of a size (it warms the caches the capture must not contain), odd shapes — runs the
+    eager path;
+  * active dropout: an eager sgf_dropout launch carries its Philox seed as a launch ARGUMENT, which a capture would freeze
+    into one mask for ever.  While a step is captured, ops.dropout_res therefore draws nothing from torch's generator and
+    launches sgf_dropout_dev, which reads its seed from a slot of the capture's SEED BANK (a device int64 tensor, one slot
+    per dropout call of the forward, in call order; the backward reads the same slot) when the kernel RUNS.  Before every
+    replay — the capture step included — the host draws exactly the seeds the eager forward would have drawn
+    (`draw_seeds`: K times torch.randint(0, 2**62, (1,)) from torch's CPU generator, in call order) and copies them into
+    the bank on the current stream ahead of the graph launch: replayed steps with dropout equal the eager ones bit for bit
+    (tests/test_gpu_graphed_dropout.py).  The copy's source is one of a ring of 4 pinned buffers, each guarded by an event
+    recorded behind its copy: a buffer is rewritten only once that copy has completed, which the host finds true without
+    waiting unless it runs 4 steps ahead of the device.  A step captured under one pair of dropout probabilities is
+    re-captured when either changes.  OPT-IN: SGF_GRAPH_DROPOUT=1 turns it on; unset or 0, active dropout means eager, as
+    before it existed — measured (profiles/graphed_dropout_probe.md), the replayed step with dropout is not faster than
+    the eager one at 100 k nodes, whose two branches overlap on two streams while a captured step keeps one;
   * a replay reads its batch from a PRIVATE static input (a copy of the capture batch's features, never the caller's
     tensor), and runs only while no parameter carries a gradient (a replayed backward hands out static gradient buffers that
     autograd adopts as `p.grad`: gradient accumulation over several batches stays on the eager path);
@@ -83,11 +98,46 @@ class _PerModel(OrderedDict):
 _MIN_NODES = 4096          # below this a step is too small to matter; keep the eager path
 _SEEN_BEFORE_CAPTURE = 1   # eager batches of a size before its capture (the first one warms caches)
 _MAX_CAPTURED = 4          # captured batch sizes kept per model (each holds the activations of one step in its own pool)
+_SEED_RING = 4             # pinned staging buffers per seed bank (see _Entry.refill)
 counters = {"captures": 0, "replays": 0}      # process-wide, for tests and the bench line
 
 
 def enabled() -> bool:
     return os.environ.get("SGF_BATCH_GRAPH", "1") != "0" and ops.K.name == "hip" and torch.cuda.is_available()
+
+
+# SGF_GRAPH_DROPOUT when the variable is not set: what scripts/graphed_dropout_probe.py measured (profiles/
+# graphed_dropout_probe.md) — at 100 k nodes and d = 256 the replayed step with dropout is NOT below the eager one (4.05-4.17
+# against 3.68-3.92 ms per step on a quiet host): the eager step runs its two branches on two streams, a captured one on one
+# stream, and the device bounds the step.  Off unless asked for.
+GRAPH_DROPOUT_DEFAULT = "0"
+
+
+def graph_dropout() -> bool:
+    """SGF_GRAPH_DROPOUT=0: active dropout means the eager path, as before sgf_dropout_dev; any other value: steps with
+    active dropout are captured and replayed too."""
+    return os.environ.get("SGF_GRAPH_DROPOUT", GRAPH_DROPOUT_DEFAULT) != "0"
+
+
+def draw_seeds(k: int, out=None) -> torch.Tensor:
+    """The seeds of k consecutive eager ops.dropout_res forwards, in call order: the same draws from torch's CPU generator
+    (one torch.randint(0, 2**62, (1,)) each), written into `out[:k]` (a host int64 tensor) when given."""
+    if out is None:
+        out = torch.empty(k, dtype=torch.int64)
+    for j in range(k):
+        torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, out=out[j:j + 1])
+    return out[:k]
+
+
+def _drop_state(model):
+    """(trans_dropout, gnn_dropout) as the branches hold them now (a branch without the attribute: None)."""
+    return tuple(getattr(b, "dropout", None) for b in (model.trans_conv, model.graph_conv))
+
+
+def _fused_dropout_sites(branch) -> bool:
+    """Every dropout site of a branch works on [n, hidden] rows: ours._drop takes the fused kernel iff hidden % 4 == 0."""
+    fcs = getattr(branch, "fcs", None)
+    return fcs is not None and len(fcs) > 0 and fcs[0].out_features % 4 == 0
 
 
 class StaticCSR(ops.CSRGraph):
@@ -137,6 +187,10 @@ class _Entry:
         self.param_ptrs = None
         self.failed = False
         self.scratch = None        # the workspaces of the captured launches (kernels.begin_capture_scope)
+        self.bank = None           # kernels.SeedBank: the seeds the captured dropout launches read, one slot per call
+        self.drop = None           # the branches' dropout probabilities at capture (baked into the launches)
+        self.ring = None           # [(pinned int64 buffer, event behind its last copy)] * _SEED_RING, made on first use
+        self.turn = 0
         self.pending = None        # weakref to the last replay's backward hook until that backward has run
 
     def busy(self) -> bool:
@@ -144,10 +198,26 @@ class _Entry:
         live in the graphs' static buffers, which another replay would overwrite (two forwards before one backward)."""
         return self.pending is not None and self.pending() is not None
 
+    def refill(self):
+        """New seeds for the next replay, drawn as the eager forward draws them, copied to the bank on the current stream
+        ahead of the graph launch.  (busy() keeps a refill from falling between a replayed forward and its backward.)"""
+        k = self.bank.used if self.bank is not None else 0
+        if k == 0:
+            return
+        if self.ring is None:
+            self.ring = [(torch.empty(self.bank.seeds.numel(), dtype=torch.int64).pin_memory(), torch.cuda.Event())
+                         for _ in range(_SEED_RING)]
+        self.turn = (self.turn + 1) % _SEED_RING
+        host, copied = self.ring[self.turn]
+        copied.synchronize()              # the copy issued from this buffer _SEED_RING replays ago: long done (no-op if none)
+        draw_seeds(k, host)
+        self.bank.seeds[:k].copy_(host[:k], non_blocking=True)
+        copied.record()
+
     def release(self):
         if self.core is not None:
-            _graveyard.append((self.core, self.graph, self.scratch))           # destroyed by collect(), not here
-        self.core = self.graph = self.pending = self.scratch = None
+            _graveyard.append((self.core, self.graph, self.scratch, self.bank, self.ring))    # destroyed by collect(), not here
+        self.core = self.graph = self.pending = self.scratch = self.bank = self.ring = self.drop = None
         self.params, self.param_ptrs = (), None
 
 
@@ -165,7 +235,11 @@ def _eligible(model, x, edge_index) -> bool:
     for branch in (model.trans_conv, model.graph_conv):
         p = getattr(branch, "dropout", 1.0)        # (a branch without the attribute: unknown, stay eager)
         if p is not None and p > 0.0:
-            return False
+            # active dropout replays only on sgf_dropout_dev (seed read from the capture's seed bank), so only where every
+            # site of the branch takes the fused kernel: ATen's F.dropout would replay one frozen mask
+            if not (graph_dropout() and hasattr(branch, "dropout") and hasattr(ops.K, "dropout_dev")
+                    and _fused_dropout_sites(branch)):
+                return False
     return True
 
 
@@ -208,7 +282,10 @@ def _capture(model, entry: _Entry, x, edge_index, cdt, out_dtype):
     gc_was_on = gc.isenabled()
     gc.disable()
     from . import kernels as _kernels
+    entry.drop = _drop_state(model)
+    entry.bank = _kernels.SeedBank(dev)                  # (allocated ahead of the capture: not from the graphs' pool)
     entry.scratch = _kernels.begin_capture_scope()       # the captured launches' workspaces live (and die) with this entry
+    _kernels.begin_seed_scope(entry.bank)                # and so do the seeds their dropout launches read
     try:
         # the sample input becomes the graphs' STATIC input, into which every later replay copies its batch: a private
         # buffer, not the caller's tensor (a trainer that keeps same-sized device batches across epochs would otherwise find
@@ -217,6 +294,7 @@ def _capture(model, entry: _Entry, x, edge_index, cdt, out_dtype):
         fn = torch.cuda.make_graphed_callables(step, (x_static,) + aliases, num_warmup_iters=0, allow_unused_input=True)
     finally:
         _kernels.end_capture_scope()
+        _kernels.end_seed_scope()
         if gc_was_on:
             gc.enable()
         with torch.no_grad():           # (captured launches do not execute; kept in case a torch version warms up anyway)
@@ -254,9 +332,10 @@ def maybe_step(model, x, edge_index, cdt, out_dtype):
         return None
     csr = edge_index._sgf_csr
     nnz = int(csr[1].numel())
-    # captured launches hold the parameters' addresses and which of them get a gradient: moved (the trainer's evaluation
-    # round trip), replaced or (un)frozen parameters mean a new capture
-    stale = entry.core is not None and (nnz > entry.graph.cap or any(a is not b for a, b in zip(entry.params, model.parameters()))
+    # captured launches hold the parameters' addresses, which of them get a gradient and the dropout probabilities: moved
+    # (the trainer's evaluation round trip), replaced or (un)frozen parameters and a changed `dropout` mean a new capture
+    stale = entry.core is not None and (nnz > entry.graph.cap or entry.drop != _drop_state(model)
+                                        or any(a is not b for a, b in zip(entry.params, model.parameters()))
                                         or entry.param_ptrs != tuple((p.data_ptr(), p.requires_grad) for p in entry.params))
     if entry.core is None or stale:
         entry.release()                          # (frees the old graphs' pool before the new capture)
@@ -273,6 +352,7 @@ def maybe_step(model, x, edge_index, cdt, out_dtype):
             warnings.warn(f"sgformer_amd.graphed: capture failed, keeping the eager path for batches of {key[0]} nodes: {exc!r}")
             return None
     entry.graph.load(*csr[:3])
+    entry.refill()                          # (nothing without active dropout)
     counters["replays"] += 1
     # the graphs' output is a STATIC buffer the next replay overwrites: hand out a copy (19 MB at 100 k x 47: ~10 us), so that
     # logits a caller keeps across batches stay what they were

@@ -107,6 +107,41 @@ def end_capture_scope():
     _capture_scope = None
 
 
+class SeedBank:
+    """The dropout seeds of ONE captured step (sgformer_amd.graphed): a device int64 tensor, one slot per dropout call of the
+    forward in call order.  While a bank is the active seed scope, ops.dropout_res draws nothing from torch's generator: it
+    takes the next slot and launches sgf_dropout_dev, which reads the seed from that slot when the kernel runs.  The owner
+    rewrites slots [0, used) before every replay."""
+
+    def __init__(self, device, capacity: int = 64):
+        self.seeds = torch.zeros(int(capacity), dtype=torch.int64, device=device)
+        self.used = 0
+
+    def take(self) -> int:
+        if self.used >= self.seeds.numel():
+            raise RuntimeError(f"sgformer_amd: more than {self.seeds.numel()} dropout calls in one captured step")
+        self.used += 1
+        return self.used - 1
+
+
+_seed_scope = None         # the SeedBank of the step being captured, else None
+
+
+def begin_seed_scope(bank: SeedBank) -> SeedBank:
+    global _seed_scope
+    _seed_scope = bank
+    return bank
+
+
+def end_seed_scope():
+    global _seed_scope
+    _seed_scope = None
+
+
+def seed_scope():
+    return _seed_scope
+
+
 def _workspace(device, name: str, nbytes: int) -> torch.Tensor:
     """Per-device, per-stream scratch reused across calls (users run on that stream, in order)."""
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
@@ -897,6 +932,20 @@ class HipKernels:
         with torch.cuda.device(x.device):
             _lib.call("sgf_dropout", _ptr(x), _ld(x), _ptr(res), _ld(res), float(p), int(seed), n, d,
                       _code(x), _ptr(y), y.stride(0), _stream(x.device))
+        return y
+
+    @staticmethod
+    def dropout_dev(x, res, p: float, seeds: torch.Tensor, slot: int) -> torch.Tensor:
+        """K.dropout with the seed read from seeds[slot] (contiguous int64 on x's device) when the kernel runs."""
+        if not (seeds.dtype == torch.int64 and seeds.dim() == 1 and seeds.is_contiguous() and seeds.device == x.device):
+            raise ValueError("dropout_dev: seeds must be a contiguous 1-D int64 tensor on x's device")
+        if not 0 <= int(slot) < seeds.numel():
+            raise IndexError(f"dropout_dev: slot {slot} outside a bank of {seeds.numel()}")
+        n, d = x.shape
+        y = torch.empty((n, d), dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.call("sgf_dropout_dev", _ptr(x), _ld(x), _ptr(res), _ld(res), float(p), seeds.data_ptr() + 8 * int(slot),
+                      n, d, _code(x), _ptr(y), y.stride(0), _stream(x.device))
         return y
 
     # ---- N4: log_softmax + NLL on the training rows ----

@@ -24,6 +24,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from . import kernels as _kernels
 from .kernels import (HipKernels, LONG_ROW, _SEGMENT, _code, _ld, _one_pass_cat, _pair_gram, _ptr, _rows,  # noqa: F401
                       _rows16, _stream, _workspace, _workspaces)
 
@@ -401,6 +402,13 @@ class _DropoutRes(torch.autograd.Function):
     def forward(ctx, x, res, p: float):
         K.check(x, res)
         x, res = _rows(x), _rows(res)
+        bank = _kernels.seed_scope()
+        if bank is not None:
+            # a step being captured (sgformer_amd.graphed): no draw — the launch reads the next slot of the capture's seed
+            # bank when it runs, and the owner of the bank refills it from the generator before every replay
+            slot = bank.take()
+            ctx.meta = (float(p), (bank.seeds, slot), res is not None)
+            return K.dropout_dev(x, res, p, bank.seeds, slot)
         # a fresh 62-bit seed from torch's CPU generator: reproducible under torch.manual_seed, no sync
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64))
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -413,6 +421,8 @@ class _DropoutRes(torch.autograd.Function):
     def backward(ctx, gy):
         p, seed, has_res = ctx.meta
         gy = _rows(gy.contiguous())
+        if isinstance(seed, tuple):              # the forward's slot of the seed bank: the same mask
+            return K.dropout_dev(gy, None, p, seed[0], seed[1]), (gy if has_res else None), None
         return K.dropout(gy, None, p, seed), (gy if has_res else None), None
 
 
