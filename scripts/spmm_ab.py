@@ -14,7 +14,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sgformer_amd import ops, synth  # noqa: E402
+from sgformer_amd import _lib, ops, synth  # noqa: E402
 
 VARIANTS = {"k_spmm_wave (r01)": "wave", "k_spmm_row": "row", "k_spmm_seg": "seg", "k_spmm_seg_bf16x2": "seg2"}
 
@@ -50,7 +50,7 @@ def main():
             if force is None:
                 ops.K.spmm_tile(plan, x, n)
             else:
-                os.environ["SGF_SPMM_KERNEL"] = force    # (seg2 falls back to row for fp32 storage)
+                os.environ["SGF_SPMM_KERNEL"] = force; _lib.load().sgf_reload_env()    # (seg2 falls back to row for fp32 storage)
                 ops.K.spmm(g.rowptr, g.colind, g.val, x, n, long_segments=g.long_segments)
             b.record()
             torch.cuda.synchronize()

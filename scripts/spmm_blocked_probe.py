@@ -17,7 +17,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sgformer_amd import ops, synth  # noqa: E402
+from sgformer_amd import _lib, ops, synth  # noqa: E402
 
 
 def timed(fn, reps=5, warm=2):
@@ -104,10 +104,10 @@ def main():
         if a.ablate:
             for mask, what in ((1, "no staging loads"), (2, "no LDS entries"), (4, "no gathered entries"),
                                (6, "staging only"), (5, "LDS entries only, nothing staged"), (3, "gathered entries only")):
-                os.environ["SGF_SPMM_BLK_DEBUG"] = str(mask)
+                os.environ["SGF_SPMM_BLK_DEBUG"] = str(mask); _lib.load().sgf_reload_env()
                 report(f"  ablation [{what}] {r}x{c}", timed(lambda: ops.K.spmm_blocked(
                     g2.rowptr, plan, xp, n, long_segments=g2.long_segments)))
-            del os.environ["SGF_SPMM_BLK_DEBUG"]
+            del os.environ["SGF_SPMM_BLK_DEBUG"]; _lib.load().sgf_reload_env()
         del plan
 
 

@@ -4,7 +4,7 @@ import json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sgformer_amd import ops, synth  # noqa: E402
+from sgformer_amd import _lib, ops, synth  # noqa: E402
 dev = torch.device("cuda:0")
 n, deg = 2449029, 50.5
 ei = synth.synthetic_graph_community(n, deg, seed=123, device=dev)
@@ -17,6 +17,7 @@ os.environ["SGF_SPMM_KERNEL"] = "seg2"
 out = {}
 for rows in (128, 512, 1024, 2048, 4096, 8192, 16384, 65536):
     os.environ["SGF_SPMM_CHUNK_ROWS"] = str(rows)
+    _lib.load().sgf_reload_env()
     ts = []
     for rep in range(8):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -5,7 +5,7 @@ import json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sgformer_amd import ops, synth  # noqa: E402
+from sgformer_amd import _lib, ops, synth  # noqa: E402
 dev = torch.device("cuda:0")
 n, deg, d = 6000000, 29.0, 128
 ei = synth.synthetic_graph(n, deg, seed=7, device=dev)
@@ -17,6 +17,7 @@ out = {"n": n, "nnz": nnz, "d": d}
 ref = None
 for name in ("sub", "", "row", "seg2", "sub", ""):
     os.environ["SGF_SPMM_KERNEL"] = name      # "" = the library's own choice
+    _lib.load().sgf_reload_env()
     ts = []
     for rep in range(7):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -78,7 +78,7 @@ def main():
         print(json.dumps({"kernel": name, "ms": round(ms, 3), "frac_of_8TBps": round(alg / (ms * 1e-3) / 8e12, 4), **kw}),
               flush=True)
 
-    os.environ["SGF_SPMM_KERNEL"] = ""
+    os.environ["SGF_SPMM_KERNEL"] = ""; _lib.load().sgf_reload_env()
     t_stream = timed(lambda: ops.K.spmm(g.rowptr, g.colind, g.val, x, n, long_segments=g.long_segments, stream_hint=True))
     report("k_spmm_seg_bf16x2 (stream)", t_stream)
     y_ref = ops.K.spmm(g.rowptr, g.colind, g.val, x, n, long_segments=g.long_segments, stream_hint=True).float()

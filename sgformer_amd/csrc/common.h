@@ -44,7 +44,8 @@ void set_error(const char* fmt, ...);
 
 // ---- experiment switches: environment variables read ONCE per process, not per launch --------------------------------
 // sgf_reload_env() (include/sgf.h) makes every switch re-read its variable at its next use (probe scripts that flip a
-// switch between launches call it after changing os.environ).
+// switch between launches call it after changing os.environ).  No launcher calls getenv itself: a number is an EnvInt, a
+// word out of a fixed list an EnvWord.
 extern int g_env_epoch;
 struct EnvInt {
   const char* name;
@@ -55,6 +56,24 @@ struct EnvInt {
     if (epoch != g_env_epoch) {
       const char* e = getenv(name);
       value = (e && *e) ? atoi(e) : dflt;
+      epoch = g_env_epoch;
+    }
+    return value;
+  }
+};
+// A switch whose value is a word: its index in `words` (n of them); -1 when the variable is unset, empty or another word.
+struct EnvWord {
+  const char* name;
+  const char* const* words;
+  int n;
+  int value = -1;
+  int epoch = -1;
+  int get() {
+    if (epoch != g_env_epoch) {
+      const char* e = getenv(name);
+      value = -1;
+      for (int i = 0; e && i < n; ++i)
+        if (strcmp(e, words[i]) == 0) value = i;
       epoch = g_env_epoch;
     }
     return value;

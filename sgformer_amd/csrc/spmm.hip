@@ -24,7 +24,6 @@
 #include "spmm_shared.h"
 
 #include <climits>
-#include <string>
 #include <cstdlib>
 
 namespace sgf {
@@ -1106,12 +1105,24 @@ __global__ __launch_bounds__(512, 2) void k_spmm_blk2(
   }
 }
 
+// ---- launchers, and their experiment switches (common.h: read once, sgf_reload_env() re-reads) -----------
+EnvInt g_blk2{"SGF_SPMM_BLK2", 1};                // 0: the row-block kernel keeps its 8-byte-per-lane form (A/B)
+EnvInt g_chunk_rows{"SGF_SPMM_CHUNK_ROWS", 4096};   // rows one XCD walks at a time in the stream kernels
+#ifdef SGF_PROBES   // (make PROBES=1; the release library takes no debug mask)
+// timing experiments only, results are then wrong: 1 = skip the staging loads, 2 = skip the LDS entries, 4 = skip the
+// gathered entries
+EnvInt g_blk_debug{"SGF_SPMM_BLK_DEBUG", 0};
+#endif
+// timing experiments: the kernel of sgf_spmm / _split / _stream, whatever choose_kernel would pick
+enum Forced { kForceNone = -1, kForceWave, kForceRow, kForceSeg, kForceSeg2, kForceSub };
+const char* const kForcedWords[] = {"wave", "row", "seg", "seg2", "sub"};
+EnvWord g_forced{"SGF_SPMM_KERNEL", kForcedWords, 5};
+
 template <typename T>
 int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eval, const int32_t* nlds,
                    const int32_t* sh_ptr, const int32_t* sh_cols, const T* x, int64_t ldx, T* y, int64_t ldy,
                    int64_t n_rows, int32_t d, int32_t rows_per_block, int32_t lds_rows, hipStream_t st,
                    const LongQueue& lq, float* partial) {
-  constexpr int UNROLL = 8;
   using V = typename Stored<T>::type;
   const int threads = rows_per_block / kBlkRowsPerWave * 64;
   const size_t lds_bytes = static_cast<size_t>(lds_rows) * 64 * sizeof(V) +
@@ -1122,11 +1133,8 @@ int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eva
   if (chunk < 1) chunk = 1;
   // Two register budgets: "deep" keeps 4 KiB of gathers + 8 LDS entries in flight per wave (<= 128 VGPRs, 16 waves
   // per CU); "lean" halves both and fits 64 VGPRs, for block shapes of which the LDS admits 32 waves per CU.
-  // SGF_SPMM_BLK_DEBUG (timing experiments only, results are then wrong): 1 = skip the staging loads,
-  // 2 = skip the LDS entries, 4 = skip the gathered entries
-#ifdef SGF_PROBES   // (make PROBES=1; the release library takes no debug mask)
-  const char* dbg_env = getenv("SGF_SPMM_BLK_DEBUG");
-  const int dbg = dbg_env ? atoi(dbg_env) : 0;
+#ifdef SGF_PROBES
+  const int dbg = g_blk_debug.get();
 #else
   const int dbg = 0;
 #endif
@@ -1142,11 +1150,10 @@ int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eva
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
     attr_set[which] = lds_bytes;
   }
-  const char* v2_env = getenv("SGF_SPMM_BLK2");         // "0": keep the 8-byte-per-lane kernel (A/B)
   const uint64_t xb = static_cast<uint64_t>(n_rows) * static_cast<uint64_t>(ldx) * sizeof(T);
   if (sizeof(T) == 2 && d % 8 == 0 && d <= 256 && ldx % 8 == 0 && ldy % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
       reinterpret_cast<uintptr_t>(y) % 16 == 0 && xb < (static_cast<uint64_t>(1) << 32) && threads <= 512 &&
-      !(v2_env && v2_env[0] == '0')) {
+      g_blk2.get() != 0) {
     const size_t lds2 = static_cast<size_t>(lds_rows) * 512 + static_cast<size_t>(threads / 64) * kScratchPerWave;
     auto fn2 = &k_spmm_blk2<8, 4>;
     static thread_local size_t attr2 = 0;
@@ -1166,16 +1173,35 @@ int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eva
     hipLaunchKernelGGL(deep_fn, dim3(static_cast<unsigned>(nb)), dim3(threads), lds_bytes, st, rowptr, ecode, eval,
                        nlds, sh_ptr, sh_cols, x, ldx, y, ldy, n_rows, d, rows_per_block, lds_rows, chunk, lq, dbg);
   SGF_LAUNCH_CHECK();
-  if (lq.cap > 0) {
-    const dim3 block(kWavesPerBlock * 64);
-    const int nbl = lq.cap < 2048 ? lq.cap : 2048;
-    hipLaunchKernelGGL((k_spmm_long_seg<T, UNROLL>), dim3(nbl), block, 0, st, rowptr, ecode, eval, x, ldx, d, lq,
-                       partial);
-    SGF_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_spmm_long_fin<T>), dim3(nbl), dim3(256), 0, st, lq, partial, d, y, ldy);
-    SGF_LAUNCH_CHECK();
+  // (long rows keep plain source ids and values in the plan's entry arrays)
+  return spmm_long_rows(sizeof(T) == 2 ? SGF_BF16 : SGF_F32, rowptr, ecode, eval, x, ldx, d, lq, partial, y, ldy, st);
+}
+
+// Which kernel serves sgf_spmm / _split / _stream (A/B on one MI355X, ogbn-products scale, profiles/r02_spmm_structured.md):
+//   gathers out of HBM (uniform graph)      wave 10.46  row 10.49  seg 10.65  seg_bf16x2 10.66 ms  -> row
+//   gathers out of L2 (re-ordered, bf16)    wave  3.94  row  3.84  seg  3.96  seg_bf16x2  3.31 ms  -> seg_bf16x2
+//   gathers out of L2 (re-ordered, fp32)    wave  6.00  row  5.97  seg  7.37                       -> row
+// `stream` is the caller's statement that the CSR's gathers mostly hit in L2 (sgf_spmm_stream); `fits32`: d <= 256 and
+// 32-bit offsets reach all of X; `pair_ok`: d, ldx, ldy multiples of 8 and x, y 16-byte aligned (with 2-byte elements the
+// stream kernel then fetches two rows per 16-byte-per-lane load).
+// 64 < d <= 128, bf16 (the 100M recipe's hidden width), stream or not: the stream kernel with half of each half-wave idle
+// still beats the half-wave-per-row kernel — 7.26 vs 8.39 ms = 6.35 vs 5.5 TB/s of 256-byte gathers on a uniform graph of
+// 6 M nodes, degree 29 (scripts/spmm_d128_probe.py): no per-row tail of dependent single loads, no idle half when the
+// two rows of a wave differ in length.
+// `forced` (SGF_SPMM_KERNEL) overrides what it can: seg2 needs bf16 pairs (else row), seg and row need fits32 (else
+// wave), sub only undoes the narrow-stream rule; any other d <= 128 is always Sub and d > 256 always Wave.
+enum class Arm { SegBf16x2, Seg, Row, Wave, Sub };
+struct Choice { Arm arm; int lanes_per_row; };   // lanes_per_row: Sub only
+Choice choose_kernel(int32_t d, size_t elem_size, bool fits32, bool pair_ok, bool stream, int forced) {
+  const bool pairs = fits32 && elem_size == 2 && pair_ok;
+  const bool narrow_stream = d > 64 && d <= 128 && pairs && forced != kForceSub;
+  if (d > 128 || narrow_stream) {
+    if (pairs && (stream || forced == kForceSeg2 || (narrow_stream && forced == kForceNone))) return {Arm::SegBf16x2, 0};
+    if (fits32 && forced == kForceSeg) return {Arm::Seg, 0};
+    if (fits32 && forced != kForceWave) return {Arm::Row, 0};
+    return {Arm::Wave, 0};
   }
-  return SGF_OK;
+  return {Arm::Sub, d > 64 ? 32 : d > 32 ? 16 : d > 16 ? 8 : d > 8 ? 4 : d > 4 ? 2 : 1};
 }
 
 template <typename T>
@@ -1184,69 +1210,56 @@ int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const
            float* partial, bool stream) {
   constexpr int UNROLL = 8;
   const dim3 block(kWavesPerBlock * 64);
-  const char* force = getenv("SGF_SPMM_KERNEL");          // timing experiments: wave | row | seg | seg2 | sub
-  const std::string fk = force ? force : "";
   const uint64_t x_bytes = static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * sizeof(T);
-  const bool fits32 = d <= 256 && n_cols > 0 && x_bytes < (static_cast<uint64_t>(1) << 32);   // 32-bit offsets reach all of X
-  const bool pair_ok = sizeof(T) == 2 && d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 &&
-                       reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0;
-  // 64 < d <= 128, bf16 (the 100M recipe's hidden width): the stream kernel with half of each half-wave idle still
-  // beats the half-wave-per-row kernel — 7.26 vs 8.39 ms = 6.35 vs 5.5 TB/s of 256-byte gathers on a uniform graph of
-  // 6 M nodes, degree 29 (scripts/spmm_d128_probe.py): no per-row tail of dependent single loads, no idle half when the
-  // two rows of a wave differ in length
-  const bool narrow_stream = d > 64 && d <= 128 && fits32 && pair_ok && fk != "sub";
-  if (d > 128 || narrow_stream) {
-    const int64_t nb = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-    // Kernel choice (A/B on one MI355X, ogbn-products scale, profiles/r02_spmm_structured.md):
-    //   gathers out of HBM (uniform graph)      wave 10.46  row 10.49  seg 10.65  seg_bf16x2 10.66 ms  -> row
-    //   gathers out of L2 (re-ordered, bf16)    wave  3.94  row  3.84  seg  3.96  seg_bf16x2  3.31 ms  -> seg_bf16x2
-    //   gathers out of L2 (re-ordered, fp32)    wave  6.00  row  5.97  seg  7.37                       -> row
-    // `stream` is the caller's statement that the CSR's gathers mostly hit in L2 (sgf_spmm_stream).
-    const int64_t nbs = (n_rows + kWavesPerBlock * kSegRows - 1) / (kWavesPerBlock * kSegRows);
-    int chunk_rows = 4096;                                   // one XCD walks ~4096 consecutive rows at a time
-    if (const char* e = getenv("SGF_SPMM_CHUNK_ROWS")) chunk_rows = atoi(e) > 0 ? atoi(e) : chunk_rows;   // experiments
-    const int chunk = chunk_rows / (kWavesPerBlock * kSegRows) > 0 ? chunk_rows / (kWavesPerBlock * kSegRows) : 1;
-    if (fits32 && pair_ok && (stream || fk == "seg2" || (narrow_stream && fk.empty())))
+  const bool fits32 = d <= 256 && n_cols > 0 && x_bytes < (static_cast<uint64_t>(1) << 32);
+  const bool pair_ok = d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
+                       reinterpret_cast<uintptr_t>(y) % 16 == 0;
+  const Choice c = choose_kernel(d, sizeof(T), fits32, pair_ok, stream, g_forced.get());
+  const int64_t nb = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;                              // a wave per row
+  const int64_t nbs = (n_rows + kWavesPerBlock * kSegRows - 1) / (kWavesPerBlock * kSegRows);     // a wave per kSegRows rows
+  const int chunk_rows = g_chunk_rows.get() > 0 ? g_chunk_rows.get() : 4096;   // one XCD walks ~4096 consecutive rows at a time
+  const int chunk = chunk_rows / (kWavesPerBlock * kSegRows) > 0 ? chunk_rows / (kWavesPerBlock * kSegRows) : 1;
+#define SGF_SUB(LPR_)                                                                         \
+  case LPR_: {                                                                                \
+    constexpr int RPB = kWavesPerBlock * (64 / LPR_);                                         \
+    const int64_t nbr = (n_rows + RPB - 1) / RPB;                                             \
+    hipLaunchKernelGGL((k_spmm_sub<T, LPR_, UNROLL>), dim3(static_cast<unsigned>(nbr)), block, \
+                       0, st, rowptr, colind, val, x, ldx, y, ldy, n_rows, d, lq);            \
+  } break;
+  switch (c.arm) {
+    case Arm::SegBf16x2:
       hipLaunchKernelGGL((k_spmm_seg_bf16x2<16>), dim3(static_cast<unsigned>(nbs)), block, 0, st, rowptr, colind, val,
                          reinterpret_cast<const uint16_t*>(x), static_cast<uint32_t>(ldx * sizeof(T)),
                          static_cast<uint32_t>(x_bytes), reinterpret_cast<uint16_t*>(y), ldy, n_rows, d, chunk, lq);
-    else if (fits32 && fk == "seg")
+      break;
+    case Arm::Seg:
       hipLaunchKernelGGL((k_spmm_seg<T, (sizeof(T) == 4 ? 8 : 16)>), dim3(static_cast<unsigned>(nbs)), block, 0, st,
                          rowptr, colind, val, x, static_cast<uint32_t>(ldx * sizeof(T)),
                          static_cast<uint32_t>(x_bytes), y, ldy, n_rows, d, chunk, lq);
-    else if (fits32 && fk != "wave")
+      break;
+    case Arm::Row:
       hipLaunchKernelGGL((k_spmm_row<T, UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st, rowptr, colind,
                          val, x, static_cast<uint32_t>(ldx * sizeof(T)), static_cast<uint32_t>(x_bytes), y, ldy,
                          n_rows, d, lq);
-    else
+      break;
+    case Arm::Wave:
       hipLaunchKernelGGL((k_spmm_wave<T, UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st,
                          rowptr, colind, val, x, ldx, y, ldy, n_rows, d, lq);
-  } else {
-#define SGF_SUB(LPR_)                                                                         \
-  {                                                                                           \
-    constexpr int RPB = kWavesPerBlock * (64 / LPR_);                                         \
-    const int64_t nb = (n_rows + RPB - 1) / RPB;                                              \
-    hipLaunchKernelGGL((k_spmm_sub<T, LPR_, UNROLL>), dim3(static_cast<unsigned>(nb)), block, \
-                       0, st, rowptr, colind, val, x, ldx, y, ldy, n_rows, d, lq);            \
+      break;
+    case Arm::Sub:
+      switch (c.lanes_per_row) {
+        SGF_SUB(32)
+        SGF_SUB(16)
+        SGF_SUB(8)
+        SGF_SUB(4)
+        SGF_SUB(2)
+        SGF_SUB(1)
+      }
+      break;
   }
-    if (d > 64) SGF_SUB(32)
-    else if (d > 32) SGF_SUB(16)
-    else if (d > 16) SGF_SUB(8)
-    else if (d > 8) SGF_SUB(4)
-    else if (d > 4) SGF_SUB(2)
-    else SGF_SUB(1)
 #undef SGF_SUB
-  }
   SGF_LAUNCH_CHECK();
-  if (lq.cap > 0) {
-    const int nb = lq.cap < 2048 ? lq.cap : 2048;
-    hipLaunchKernelGGL((k_spmm_long_seg<T, UNROLL>), dim3(nb), block, 0, st, rowptr, colind, val, x, ldx, d,
-                       lq, partial);
-    SGF_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_spmm_long_fin<T>), dim3(nb), dim3(256), 0, st, lq, partial, d, y, ldy);
-    SGF_LAUNCH_CHECK();
-  }
-  return SGF_OK;
+  return spmm_long_rows(sizeof(T) == 2 ? SGF_BF16 : SGF_F32, rowptr, colind, val, x, ldx, d, lq, partial, y, ldy, st);
 }
 
 }  // namespace
@@ -1278,6 +1291,19 @@ int spmm_long_rows(int dtype, const int64_t* rowptr, const int32_t* colind, cons
 using namespace sgf;
 
 namespace {
+// What every row kernel asks of x [*, d] and y [n_rows, d]: a known dtype, d and both leading dimensions multiples of 4
+// elements, rows at least d long, both bases aligned to 4 elements.
+int check_spmm_operands(const char* fn, const void* x, int64_t ldx, const void* y, int64_t ldy, int32_t d, int32_t dtype) {
+  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
+  SGF_REQUIRE(d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, SGF_E_INVALID,
+              "%s: d, ldx, ldy must be multiples of 4 with ld >= d (d=%d ldx=%lld ldy=%lld)", fn, d,
+              static_cast<long long>(ldx), static_cast<long long>(ldy));
+  const size_t esz = dtype == SGF_BF16 ? 2 : 4;
+  SGF_REQUIRE(reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0 && reinterpret_cast<uintptr_t>(y) % (4 * esz) == 0,
+              SGF_E_INVALID, "%s: x / y must be aligned to 4 elements", fn);
+  return SGF_OK;
+}
+
 int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,
                 int64_t n_cols, void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, const LongQueue& lq,
                 float* partial, hipStream_t st, const char* fn, bool stream = false) {
@@ -1286,21 +1312,12 @@ int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, 
   SGF_REQUIRE(rowptr && x && y, SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE(n_rows < (static_cast<int64_t>(1) << 31) * kWavesPerBlock, SGF_E_UNSUPPORTED,
               "%s: n_rows too large for one launch", fn);
-  SGF_REQUIRE(d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, SGF_E_INVALID,
-              "%s: d, ldx, ldy must be multiples of 4 with ld >= d (d=%d ldx=%lld ldy=%lld)", fn, d,
-              static_cast<long long>(ldx), static_cast<long long>(ldy));
-  const size_t esz = dtype == SGF_BF16 ? 2 : 4;
-  SGF_REQUIRE(reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0 &&
-                  reinterpret_cast<uintptr_t>(y) % (4 * esz) == 0,
-              SGF_E_INVALID, "%s: x / y must be aligned to 4 elements", fn);
+  if (const int rc = check_spmm_operands(fn, x, ldx, y, ldy, d, dtype)) return rc;
   if (dtype == SGF_F32)
     return launch<float>(rowptr, colind, val, static_cast<const float*>(x), ldx, n_cols, static_cast<float*>(y), ldy,
                          n_rows, d, st, lq, partial, stream);
-  if (dtype == SGF_BF16)
-    return launch<uint16_t>(rowptr, colind, val, static_cast<const uint16_t*>(x), ldx, n_cols,
-                            static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream);
-  set_error("%s: unknown dtype %d", fn, dtype);
-  return SGF_E_INVALID;
+  return launch<uint16_t>(rowptr, colind, val, static_cast<const uint16_t*>(x), ldx, n_cols,
+                          static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream);
 }
 }  // namespace
 
@@ -1316,33 +1333,36 @@ extern "C" int32_t sgf_spmm_segment_len(void) { return kSegLen; }
 
 extern "C" size_t sgf_spmm_split_workspace_bytes(int64_t long_segments, int32_t d) {
   if (long_segments < 0 || d < 0) return 0;
-  return 256 + align_up(static_cast<size_t>(long_segments) * sizeof(LongEntry), 256) +
-         static_cast<size_t>(long_segments) * static_cast<size_t>(d) * sizeof(float);
+  return long_partial_off(long_segments) + static_cast<size_t>(long_segments) * static_cast<size_t>(d) * sizeof(float);
+}
+
+int sgf::spmm_long_queue(const char* fn, int64_t long_len, int64_t long_segments, int32_t d, void* workspace,
+                         size_t workspace_bytes, hipStream_t st, LongQueue* lq, float** partial) {
+  SGF_REQUIRE(long_len >= 1 && long_segments >= 0 && long_segments < (static_cast<int64_t>(1) << 31),
+              SGF_E_INVALID, "%s: bad long_len / long_segments", fn);
+  *lq = LongQueue{nullptr, nullptr, 0, INT64_MAX};
+  *partial = nullptr;
+  if (long_segments == 0) return SGF_OK;
+  SGF_REQUIRE(workspace && workspace_bytes >= sgf_spmm_split_workspace_bytes(long_segments, d),
+              SGF_E_WORKSPACE, "%s: workspace too small", fn);
+  char* ws = static_cast<char*>(workspace);
+  lq->count = reinterpret_cast<int32_t*>(ws + kLongCountOff);
+  lq->entries = reinterpret_cast<LongEntry*>(ws + kLongEntriesOff);
+  lq->cap = static_cast<int32_t>(long_segments);
+  lq->long_len = long_len;
+  *partial = reinterpret_cast<float*>(ws + long_partial_off(long_segments));
+  SGF_CHECK_HIP(hipMemsetAsync(lq->count, 0, sizeof(int32_t), st));
+  return SGF_OK;
 }
 
 static int spmm_split_impl(bool stream_hint, const char* fn, const int64_t* rowptr, const int32_t* colind, const float* val,
                               const void* x, int64_t ldx, int64_t n_cols, void* y, int64_t ldy, int64_t n_rows,
                               int32_t d, int32_t dtype, int64_t long_len, int64_t long_segments,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  SGF_REQUIRE(long_len >= 1 && long_segments >= 0 && long_segments < (static_cast<int64_t>(1) << 31),
-              SGF_E_INVALID, "%s: bad long_len / long_segments", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (long_segments == 0) {
-    const LongQueue none{nullptr, nullptr, 0, INT64_MAX};
-    return spmm_common(rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype, none, nullptr, st, fn,
-                       stream_hint);
-  }
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_spmm_split_workspace_bytes(long_segments, d),
-              SGF_E_WORKSPACE, "%s: workspace too small", fn);
-  char* ws = static_cast<char*>(workspace);
   LongQueue lq;
-  lq.count = reinterpret_cast<int32_t*>(ws);
-  lq.entries = reinterpret_cast<LongEntry*>(ws + 256);
-  lq.cap = static_cast<int32_t>(long_segments);
-  lq.long_len = long_len;
-  float* partial = reinterpret_cast<float*>(
-      ws + 256 + align_up(static_cast<size_t>(long_segments) * sizeof(LongEntry), 256));
-  SGF_CHECK_HIP(hipMemsetAsync(lq.count, 0, sizeof(int32_t), st));
+  float* partial;
+  if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
   return spmm_common(rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype, lq, partial, st, fn, stream_hint);
 }
 
@@ -1379,35 +1399,17 @@ extern "C" int sgf_spmm_blocked(const int64_t* rowptr, const int32_t* ecode, con
   SGF_REQUIRE(n_rows >= 0 && d >= 0, SGF_E_INVALID, "%s: negative size", fn);
   if (n_rows == 0 || d == 0) return SGF_OK;
   SGF_REQUIRE(rowptr && ecode && eval && nlds && sh_ptr && sh_cols && x && y, SGF_E_INVALID, "%s: null pointer", fn);
-  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
   SGF_REQUIRE(d <= 256, SGF_E_UNSUPPORTED, "%s: d = %d > 256 (one wave per row)", fn, d);
   SGF_REQUIRE(rows_per_block >= kBlkRowsPerWave && rows_per_block <= 128 && rows_per_block % kBlkRowsPerWave == 0,
               SGF_E_INVALID, "%s: rows_per_block must be a multiple of %d in [%d, 128]", fn, kBlkRowsPerWave,
               kBlkRowsPerWave);
   SGF_REQUIRE(lds_rows >= 1 && lds_rows <= sgf_spmm_lds_rows_len(dtype), SGF_E_INVALID,
               "%s: lds_rows %d outside [1, %d]", fn, lds_rows, sgf_spmm_lds_rows_len(dtype));
-  SGF_REQUIRE(d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= d && ldy >= d, SGF_E_INVALID,
-              "%s: d, ldx, ldy must be multiples of 4 with ld >= d", fn);
-  const size_t esz = dtype == SGF_BF16 ? 2 : 4;
-  SGF_REQUIRE(reinterpret_cast<uintptr_t>(x) % (4 * esz) == 0 && reinterpret_cast<uintptr_t>(y) % (4 * esz) == 0,
-              SGF_E_INVALID, "%s: x / y must be aligned to 4 elements", fn);
-  SGF_REQUIRE(long_len >= 1 && long_segments >= 0 && long_segments < (static_cast<int64_t>(1) << 31),
-              SGF_E_INVALID, "%s: bad long_len / long_segments", fn);
+  if (const int rc = check_spmm_operands(fn, x, ldx, y, ldy, d, dtype)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LongQueue lq{nullptr, nullptr, 0, long_len};
-  float* partial = nullptr;
-  if (long_segments > 0) {
-    SGF_REQUIRE(workspace && workspace_bytes >= sgf_spmm_split_workspace_bytes(long_segments, d), SGF_E_WORKSPACE,
-                "%s: workspace too small", fn);
-    char* ws = static_cast<char*>(workspace);
-    lq.count = reinterpret_cast<int32_t*>(ws);
-    lq.entries = reinterpret_cast<LongEntry*>(ws + 256);
-    lq.cap = static_cast<int32_t>(long_segments);
-    partial = reinterpret_cast<float*>(ws + 256 + align_up(static_cast<size_t>(long_segments) * sizeof(LongEntry), 256));
-    SGF_CHECK_HIP(hipMemsetAsync(lq.count, 0, sizeof(int32_t), st));
-  } else {
-    lq.long_len = INT64_MAX;   // no queue: every row is walked by its wave (the plan then has LDS codes everywhere)
-  }
+  LongQueue lq;   // (without a queue every row is walked by its wave: the plan then has LDS codes everywhere)
+  float* partial;
+  if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
   if (dtype == SGF_F32)
     return launch_blocked<float>(rowptr, ecode, eval, nlds, sh_ptr, sh_cols, static_cast<const float*>(x), ldx,
                                  static_cast<float*>(y), ldy, n_rows, d, rows_per_block, lds_rows, st, lq, partial);

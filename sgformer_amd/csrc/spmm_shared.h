@@ -56,6 +56,19 @@ static __device__ __forceinline__ void push_long_row(const LongQueue& q, int64_t
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// The long-row workspace (sgf_spmm_split_workspace_bytes): the queue's counter, its entries, one fp32 partial row of d
+// values per segment — each part 256-byte aligned.
+constexpr size_t kLongCountOff = 0, kLongEntriesOff = 256;
+static inline size_t long_partial_off(int64_t long_segments) {
+  return kLongEntriesOff + align_up(static_cast<size_t>(long_segments) * sizeof(LongEntry), 256);
+}
+
+// The queue of one launch, carved from `workspace` with its counter zeroed on `st`, and the partial rows behind it; with
+// long_segments == 0 no queue (cap 0, long_len INT64_MAX: no row is ever queued) and no workspace.  `fn` names the entry
+// in the messages: SGF_E_INVALID for long_len < 1 or long_segments outside [0, 2^31), SGF_E_WORKSPACE for a workspace
+// that is null or smaller than sgf_spmm_split_workspace_bytes(long_segments, d).
+int spmm_long_queue(const char* fn, int64_t long_len, int64_t long_segments, int32_t d, void* workspace,
+                    size_t workspace_bytes, hipStream_t st, LongQueue* lq, float** partial);
 
 // Rows queued by a SpMM kernel (LongQueue) reduced by whole workgroups and written to y (spmm.hip).
 int spmm_long_rows(int dtype, const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,

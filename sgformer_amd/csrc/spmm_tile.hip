@@ -616,22 +616,10 @@ extern "C" int sgf_spmm_tile(const int32_t* blk_row, int64_t nb, int32_t block_r
               SGF_E_INVALID, "%s: x / y rows must be 16-byte aligned (ld %% 8 == 0)", fn);
   const uint64_t x_bytes = static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * 2;
   SGF_REQUIRE(x_bytes < (static_cast<uint64_t>(1) << 32) - 2048, SGF_E_UNSUPPORTED, "%s: x beyond 4 GiB (32-bit gather offsets)", fn);
-  SGF_REQUIRE(long_len >= 1 && long_segments >= 0 && long_segments < (static_cast<int64_t>(1) << 31), SGF_E_INVALID,
-              "%s: bad long_len / long_segments", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LongQueue lq{nullptr, nullptr, 0, INT64_MAX};
-  float* partial = nullptr;
-  if (long_segments > 0) {
-    SGF_REQUIRE(workspace && workspace_bytes >= sgf_spmm_split_workspace_bytes(long_segments, d), SGF_E_WORKSPACE,
-                "%s: workspace too small", fn);
-    char* ws = static_cast<char*>(workspace);
-    lq.count = reinterpret_cast<int32_t*>(ws);
-    lq.entries = reinterpret_cast<LongEntry*>(ws + 256);
-    lq.cap = static_cast<int32_t>(long_segments);
-    lq.long_len = long_len;
-    partial = reinterpret_cast<float*>(ws + 256 + align_up(static_cast<size_t>(long_segments) * sizeof(LongEntry), 256));
-    SGF_CHECK_HIP(hipMemsetAsync(lq.count, 0, sizeof(int32_t), st));
-  }
+  LongQueue lq;
+  float* partial;
+  if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
   TilePlanArgs P{blk_row, sh_ptr, sh_cols, tile_ptr, grp, static_cast<const uint4*>(pool), rem_rowptr, rem_col, rem_val};
   // SGF_SPMM_TILE_DEBUG (timing experiments only, results are then wrong): 1 = skip the tile phase, 2 = skip the gathers,
   // 4 / 512 = nt staged rows / packed tiles, 8 / 256 = nt / write-through (sc1) y stores, 16 = gathers clamped to 4096 rows (L2 hits), 32 = no multiply-adds in the gather

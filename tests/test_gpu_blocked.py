@@ -256,3 +256,26 @@ def test_spmm_stream_vs_oracle(cuda, dtype, name, d):
     assert _rel(y.float(), torch.from_numpy(ref)) <= (1e-6 if dtype == torch.float32 else 3e-3)
     y2 = ops.K.spmm(g.rowptr, g.colind, g.val, xs.to(cuda), n, long_segments=g.long_segments, stream_hint=True)
     assert torch.equal(y, y2)                                # deterministic
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_spmm_blocked_long_row_at_d64(cuda, dtype):
+    """sgf_spmm_blocked with a long-row queue at d = 64 (the hub cases of test_spmm_blocked_vs_oracle are all d = 256):
+    2048 nodes of degree about 6, one row of more than 1500 entries = two segments of the queue, 64 rows per block."""
+    from sgformer_amd import ops, synth
+    n, d = 2048, 64
+    g0 = torch.Generator().manual_seed(11)
+    hub = torch.stack([torch.randint(0, n, (1500,), generator=g0), torch.full((1500,), 33)])
+    ei = torch.cat([synth.synthetic_graph(n, 6.0, seed=3), hub], dim=1)
+    g = ops.CSRGraph(ei.to(cuda), n)
+    rowptr, colind, val, _ = O.csr_build(ei.numpy(), n)
+    lens = np.diff(rowptr)
+    assert ops.LONG_ROW < lens[33] <= 2 * ops.LONG_ROW and g.long_segments >= 2
+    plan = ops.BlockedPlan(g.rowptr, g.colind, g.val, n, dtype, rows_per_block=64, lds_rows=64)
+    torch.manual_seed(3)
+    xs = torch.randn(n, d).to(dtype)
+    y = ops.K.spmm_blocked(g.rowptr, plan, xs.to(cuda), n, long_segments=g.long_segments)
+    ref = np.zeros((n, d))
+    np.add.at(ref, np.repeat(np.arange(n), lens), val[:, None].astype(np.float64) * xs.double().numpy()[colind])
+    # (a hub row left out or summed wrongly would alone be an error of 1 / sqrt(n) = 2e-2: its norm is a typical row's)
+    assert _rel(y.float(), torch.from_numpy(ref)) <= (1e-6 if dtype == torch.float32 else 3e-3)
