@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 660 /* 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 661 /* 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -444,6 +444,14 @@ int sgf_pad_rows(const void* src, int64_t lds, int32_t src_dtype, int64_t n_src,
  * ------------------------------------------------------------------------------------------ */
 int64_t sgf_attn_stats_len(int32_t heads, int32_t d);
 size_t sgf_attn_workspace_bytes(int64_t n, int32_t heads, int32_t d);
+/* Geometry of the persistent row kernels behind the sgf_attn_* / sgf_attn_h_* entries (host queries, no GPU needed): a launch
+ * has at most sgf_attn_max_blocks() workgroups, and workgroup b walks the row tiles b, b + grid, ... of
+ * sgf_attn_tile_rows(kind, d, dtype) rows each; kind 0 = the reduce kernels (sgf_attn_fwd_reduce / _bwd_reduce /
+ * _h_bwd_reduce, sgf_gram's own kernel), kind 1 = the apply kernels.  d is padded to 64 / 128 / 256; dtype SGF_F32 or SGF_BF16.
+ * -1 for an unknown kind, width or dtype.  (bf16 sgf_attn_h_fwd / _h_bwd_apply at d in {64, 128, 256} with 16-byte rows run
+ * csrc/rowgemm.hip instead: 32-row tiles per WAVE.) */
+int32_t sgf_attn_max_blocks(void);
+int32_t sgf_attn_tile_rows(int32_t kind, int32_t d, int32_t dtype);
 
 int sgf_attn_fwd_reduce(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
                         int64_t ldv, int64_t n, int32_t heads, int32_t v_heads, int32_t d,

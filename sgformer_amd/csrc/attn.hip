@@ -1305,10 +1305,13 @@ int launch_reduce(const ReduceArgs& args, int DP, int nblk, hipStream_t st) {
 // whose MFMA / epilogue phases interleave; 2 -> one 135 KiB block per CU with twice the tile.
 constexpr int kApplyRB = 2;  // RB = 1 spills at DP = 256 (the resident B strip alone is 64 VGPRs of the 128)
 
+// rows per tile: k_attn_apply 32 * (8 / (DP/32));  k_apply_bf16 32 * kApplyRB * (8 / (DP/32))
+template <typename T>
+inline int apply_rows_per_tile(int DP) { return (sizeof(T) == 4 ? 32 : 32 * kApplyRB) * (8 / (DP / 32)); }
+
 template <typename T, int MODE>
 int launch_apply(const ApplyArgs& args, int DP, hipStream_t st) {
-  // rows per tile: k_attn_apply 32 * (8 / (DP/32));  k_apply_bf16 32 * kApplyRB * (8 / (DP/32))
-  const int RT = (sizeof(T) == 4 ? 32 : 32 * kApplyRB) * (8 / (DP / 32));
+  const int RT = apply_rows_per_tile<T>(DP);
   int64_t ntiles = (args.n + RT - 1) / RT;
   const int64_t maxblk = (sizeof(T) == 2 && kApplyRB == 1) ? 2 * kMaxBlocks : kMaxBlocks;
   const int nblk = static_cast<int>(ntiles < maxblk ? ntiles : maxblk);
@@ -1885,6 +1888,21 @@ extern "C" int sgf_attn_h_bwd_post(const void* h, int64_t ldh, int64_t n, int32_
   SGF_REQUIRE(!addend || (reinterpret_cast<uintptr_t>(addend) % 16 == 0 && ldadd % 8 == 0 && ldadd >= d), SGF_E_INVALID,
               "sgf_attn_h_bwd_post: addend rows must be 16-byte aligned");
   return hrow_bwd_post(h, ldh, n, d, D, ds, workspace, addend, ldadd, dh, lddh, static_cast<hipStream_t>(stream));
+}
+
+// host queries for the persistent kernels' geometry (include/sgf.h): the launchers' own constants, no second table
+extern "C" int32_t sgf_attn_max_blocks(void) { return kMaxBlocks; }
+
+extern "C" int32_t sgf_attn_tile_rows(int32_t kind, int32_t d, int32_t dtype) {
+  if (d < 1 || d > 256 || (dtype != SGF_F32 && dtype != SGF_BF16) || (kind != 0 && kind != 1)) return -1;
+  const int DP = padded_dim(d);
+  if (kind == 1) return dtype == SGF_F32 ? apply_rows_per_tile<float>(DP) : apply_rows_per_tile<uint16_t>(DP);
+  // every reduce mode of one storage type walks the same tile height (the bf16 wave count differs, the rows do not)
+  const int r = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeFwd>(DP) : reduce_rows_per_tile<uint16_t, kModeFwd>(DP);
+  const int rb = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeBwd>(DP) : reduce_rows_per_tile<uint16_t, kModeBwd>(DP);
+  const int rh = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeBwdH>(DP) : reduce_rows_per_tile<uint16_t, kModeBwdH>(DP);
+  const int rg = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeGram>(DP) : reduce_rows_per_tile<uint16_t, kModeGram>(DP);
+  return (r == rb && r == rh && r == rg) ? r : -1;
 }
 
 extern "C" int64_t sgf_attn_stats_len(int32_t heads, int32_t d) {
