@@ -1281,6 +1281,16 @@ inline int reduce_row_groups(int DP) {
   return DP == 64 ? ReduceGeom<NW, 64>::RG : (DP == 128 ? ReduceGeom<NW, 128>::RG : ReduceGeom<NW, 256>::RG);
 }
 
+// grid of a persistent kernel: one block per tile of R rows, `cap` blocks at the most
+inline int persistent_blocks(int64_t n, int R, int64_t cap = kMaxBlocks) {
+  const int64_t ntiles = (n + R - 1) / R;
+  return static_cast<int>(ntiles < cap ? ntiles : cap);
+}
+
+// f(T{}) with the storage type of a checked dtype code: float for SGF_F32, uint16_t for SGF_BF16
+template <typename F>
+inline int by_dtype(int dtype, F&& f) { return dtype == SGF_F32 ? f(float{}) : f(uint16_t{}); }
+
 template <typename T, int MODE>
 int launch_reduce(const ReduceArgs& args, int DP, int nblk, hipStream_t st) {
   const dim3 grid(nblk, args.heads), block(sizeof(T) == 2 ? bf_reduce_waves(MODE) * 64 : kRedThreads);
@@ -1301,6 +1311,87 @@ int launch_reduce(const ReduceArgs& args, int DP, int nblk, hipStream_t st) {
   return SGF_OK;
 }
 
+// What every reduce sets: one head, operand b not shared, unit scale (the attention stages overwrite those three).
+ReduceArgs reduce_args(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t n, int d, int db, void* ws) {
+  ReduceArgs r{};
+  r.a = a; r.lda = lda; r.b = b; r.ldb = ldb;
+  r.n = n; r.d = d; r.db = db; r.heads = 1; r.b_heads = 1; r.gscale = 1.f;
+  r.partial = static_cast<float*>(ws);
+  return r;
+}
+
+// The reduce of every entry without (or outside) an LDS-DMA path: one block per tile of the mode's height.  *nblk partials of
+// *RG row groups are left for the entry's finalize.
+template <typename T, int MODE>
+int reduce_and_count(const ReduceArgs& r, int DP, int* nblk, int* RG, hipStream_t st) {
+  *nblk = persistent_blocks(r.n, reduce_rows_per_tile<T, MODE>(DP));
+  *RG = reduce_row_groups<T, MODE>(DP);
+  return launch_reduce<T, MODE>(r, DP, *nblk, st);
+}
+
+// ---- the finalize launches: `nblk` partials of geometry (DP, RG) added in a fixed order.  The LDS-DMA paths (csrc/gramx.hip,
+// csrc/gram_f32x.hip) leave DP = 256, RG = 1 ----
+void launch_gram_finalize(const float* part, int nblk, int m, int k, int DP, int RG, float* c, int64_t ldc, float* colsum,
+                          hipStream_t st) {
+  const int64_t len = static_cast<int64_t>(m) * k + m;
+  hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, part, nblk, m,
+                     k, DP, RG, c, ldc, colsum);
+}
+
+int finalize_gram(const float* part, int nblk, int m, int k, int DP, int RG, float* c, int64_t ldc, float* colsum,
+                  hipStream_t st) {
+  launch_gram_finalize(part, nblk, m, k, DP, RG, c, ldc, colsum, st);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+// paired partials [role][np]: the first product with A's column sums, the second without
+int finalize_gram_pair(const float* part, int np, int m, int k, int DP, int RG, float* c1, int64_t ldc1, float* colsum, float* c2,
+                       int64_t ldc2, hipStream_t st) {
+  launch_gram_finalize(part, np, m, k, DP, RG, c1, ldc1, colsum, st);
+  launch_gram_finalize(part + static_cast<int64_t>(np) * kPartialStride, np, m, k, DP, RG, c2, ldc2, nullptr, st);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+// d beta / d gamma of sgf_gram_ln_bwd: the second and third vector of the partials
+int finalize_ln_vectors(const float* part, int nblk, int m, float* dbeta, float* dgamma, hipStream_t st) {
+  const struct { int off; float* out; } vec[2] = {{kVecB, dbeta}, {kVecC, dgamma}};
+  for (const auto& v : vec)
+    if (v.out) hipLaunchKernelGGL(k_vec_finalize, dim3((m + 31) / 32), dim3(256), 0, st, part, nblk, v.off, m, v.out);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+int finalize_hstats(const float* part, int nblk, int d, int DP, int RG, float* hstats, hipStream_t st) {
+  const int64_t len = sgf_attn_h_bstats_len(d);
+  hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, part, nblk, d,
+                     DP, RG, hstats);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+// stats (kModeFwd) or bstats (kModeBwd): one thread per element of the longer of the two, sgf_attn_stats_len
+int finalize_attn(const float* part, int nblk, int heads, int d, int DP, int RG, int mode, float* out, hipStream_t st) {
+  const int fb = static_cast<int>((sgf_attn_stats_len(heads, d) + 255) / 256);
+  hipLaunchKernelGGL(k_attn_finalize, dim3(fb), dim3(256), 0, st, part, nblk, heads, d, DP, RG, mode, out);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+// the empty sums (n == 0) of the reduce entries, and of the Gram entries: c and whichever of the m-vectors were asked for
+int zero_floats(float* p, int64_t len, hipStream_t st) {
+  SGF_CHECK_HIP(hipMemsetAsync(p, 0, len * sizeof(float), st));
+  return SGF_OK;
+}
+
+int zero_gram_outputs(float* c, int64_t ldc, int m, int k, std::initializer_list<float*> vectors, hipStream_t st) {
+  SGF_CHECK_HIP(hipMemset2DAsync(c, ldc * sizeof(float), 0, k * sizeof(float), m, st));
+  for (float* v : vectors)
+    if (v) SGF_CHECK_HIP(hipMemsetAsync(v, 0, m * sizeof(float), st));
+  return SGF_OK;
+}
+
 // 32-row blocks per wave in k_apply_bf16: 1 -> ~68 KiB LDS, 128 VGPRs: TWO independent blocks per CU
 // whose MFMA / epilogue phases interleave; 2 -> one 135 KiB block per CU with twice the tile.
 constexpr int kApplyRB = 2;  // RB = 1 spills at DP = 256 (the resident B strip alone is 64 VGPRs of the 128)
@@ -1311,10 +1402,8 @@ inline int apply_rows_per_tile(int DP) { return (sizeof(T) == 4 ? 32 : 32 * kApp
 
 template <typename T, int MODE>
 int launch_apply(const ApplyArgs& args, int DP, hipStream_t st) {
-  const int RT = apply_rows_per_tile<T>(DP);
-  int64_t ntiles = (args.n + RT - 1) / RT;
-  const int64_t maxblk = (sizeof(T) == 2 && kApplyRB == 1) ? 2 * kMaxBlocks : kMaxBlocks;
-  const int nblk = static_cast<int>(ntiles < maxblk ? ntiles : maxblk);
+  const int nblk = persistent_blocks(args.n, apply_rows_per_tile<T>(DP),
+                                     (sizeof(T) == 2 && kApplyRB == 1) ? 2 * kMaxBlocks : kMaxBlocks);
   const dim3 grid(nblk), block(sizeof(T) == 2 ? kBfThreads : kApplyThreads);
   if (sizeof(T) == 2) {
     switch (DP) {
@@ -1348,6 +1437,14 @@ int check_common_h(const char* fn, int64_t n, int d, int dtype) {
   return check_common(fn, n, 1, d, dtype == SGF_F32_BF16X3 ? SGF_F32 : dtype);
 }
 
+// sgf_gram and sgf_gram2: any m and k that are multiples of 4 (blocks of 256), every dtype code
+int check_gram(const char* fn, int64_t n, int m, int k, int dtype) {
+  SGF_REQUIRE(n >= 0 && m >= 1 && k >= 1, SGF_E_INVALID, "%s: bad sizes n=%lld m=%d k=%d", fn, static_cast<long long>(n), m, k);
+  SGF_REQUIRE(m % 4 == 0 && k % 4 == 0, SGF_E_UNSUPPORTED, "%s: m and k must be multiples of 4 (m=%d k=%d)", fn, m, k);
+  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16 || dtype == SGF_F32_BF16X3, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
+  return SGF_OK;
+}
+
 template <typename T>
 bool aligned4(const void* p, int64_t ld) {
   return reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0 && ld % 4 == 0;
@@ -1361,48 +1458,29 @@ using namespace sgf;
 namespace {
 template <typename T>
 int gram_t(const void* a, int64_t lda, int m, const void* b, int64_t ldb, int k, int64_t n, float* c,
-           int64_t ldc, float* colsum_a, void* ws, hipStream_t st, bool x3 = false) {
+           int64_t ldc, float* colsum_a, void* ws, hipStream_t st, bool x3) {
   SGF_REQUIRE(aligned4<T>(a, lda) && aligned4<T>(b, ldb), SGF_E_INVALID,
               "sgf_gram: a / b must be 4-element aligned with ld %% 4 == 0");
+  float* part = static_cast<float*>(ws);
   for (int mi = 0; mi < m; mi += 256) {
     const int mb = m - mi < 256 ? m - mi : 256;
     for (int ki = 0; ki < k; ki += 256) {
       const int kb = k - ki < 256 ? k - ki : 256;
       const T* ap = static_cast<const T*>(a) + mi;
       const T* bp = static_cast<const T*>(b) + ki;
-      const bool f32x = sizeof(T) == 4 && x3;       // SGF_F32_BF16X3: three bf16 products (csrc/gram_f32x.hip)
-      if (f32x || (sizeof(T) == 2 && gramx_supported(ap, lda, mb, bp, ldb, kb, n))) {   // gramx: tiles by LDS-DMA
-        int nblk = 0;
-        int rc = f32x ? gram_f32x(reinterpret_cast<const float*>(ap), lda, mb, reinterpret_cast<const float*>(bp), ldb, kb, n,
-                                  static_cast<float*>(ws), &nblk, st)
-                      : gramx_gram(ap, lda, mb, bp, ldb, nullptr, 0, kb, n, static_cast<float*>(ws), &nblk, st);
-        if (rc != SGF_OK) return rc;
-        const int64_t len = static_cast<int64_t>(mb) * kb + mb;
-        float* cs = (colsum_a != nullptr && ki == 0) ? colsum_a + mi : nullptr;
-        hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st,
-                           static_cast<const float*>(ws), nblk, mb, kb, 256, 1, c + static_cast<int64_t>(mi) * ldc + ki, ldc, cs);
-        SGF_LAUNCH_CHECK();
-        continue;
+      int nblk = 0, DP = 256, RG = 1, rc;
+      if (sizeof(T) == 4 && x3) {                       // SGF_F32_BF16X3: three bf16 products (csrc/gram_f32x.hip)
+        rc = gram_f32x(reinterpret_cast<const float*>(ap), lda, mb, reinterpret_cast<const float*>(bp), ldb, kb, n, part, &nblk, st);
+      } else if (sizeof(T) == 2 && gramx_supported(ap, lda, mb, bp, ldb, kb, n)) {   // gramx: tiles by LDS-DMA
+        rc = gramx_gram(ap, lda, mb, bp, ldb, nullptr, 0, kb, n, part, &nblk, st);
+      } else {
+        DP = padded_dim(mb > kb ? mb : kb);
+        rc = reduce_and_count<T, kModeGram>(reduce_args(ap, lda, bp, ldb, n, mb, kb, ws), DP, &nblk, &RG, st);
       }
-      const int DP = padded_dim(mb > kb ? mb : kb);
-      const int R = reduce_rows_per_tile<T, kModeGram>(DP);
-      const int64_t ntiles = (n + R - 1) / R;
-      const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-      ReduceArgs r{};
-      r.a = static_cast<const T*>(a) + mi; r.lda = lda;
-      r.b = static_cast<const T*>(b) + ki; r.ldb = ldb;
-      r.q = nullptr; r.ldq = 0; r.den = nullptr;
-      r.n = n; r.d = mb; r.db = kb; r.heads = 1; r.b_heads = 1; r.gscale = 1.f;
-      r.partial = static_cast<float*>(ws);
-      int rc = launch_reduce<T, kModeGram>(r, DP, nblk, st);
       if (rc != SGF_OK) return rc;
-      const int RG = reduce_row_groups<T, kModeGram>(DP);
-      const int64_t len = static_cast<int64_t>(mb) * kb + mb;
-      float* cs = (colsum_a != nullptr && ki == 0) ? colsum_a + mi : nullptr;
-      hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0,
-                         st, r.partial, nblk, mb, kb, DP, RG, c + static_cast<int64_t>(mi) * ldc + ki,
-                         ldc, cs);
-      SGF_LAUNCH_CHECK();
+      rc = finalize_gram(part, nblk, mb, kb, DP, RG, c + static_cast<int64_t>(mi) * ldc + ki, ldc,
+                         (colsum_a != nullptr && ki == 0) ? colsum_a + mi : nullptr, st);
+      if (rc != SGF_OK) return rc;
     }
   }
   return SGF_OK;
@@ -1426,47 +1504,28 @@ extern "C" int sgf_gram_bn_bwd(const void* g1, int64_t ldg1, const void* g2, int
               "%s: bf16 storage, m and k multiples of 4 up to 256 (m=%d k=%d dtype=%d)", fn, m, k, dtype);
   SGF_REQUIRE(c && ldc >= k, SGF_E_INVALID, "%s: null c or ldc < k", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemset2DAsync(c, ldc * sizeof(float), 0, k * sizeof(float), m, st));
-    if (colsum) SGF_CHECK_HIP(hipMemsetAsync(colsum, 0, m * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_gram_outputs(c, ldc, m, k, {colsum}, st);
   SGF_REQUIRE(g1 && z && b && mean && rstd && (!training || stats), SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_gram_workspace_bytes(n, m, k), SGF_E_WORKSPACE, "%s: workspace too small", fn);
   SGF_REQUIRE(aligned4<uint16_t>(g1, ldg1) && (!g2 || aligned4<uint16_t>(g2, ldg2)) && aligned4<uint16_t>(z, ldz) &&
                   aligned4<uint16_t>(b, ldb),
               SGF_E_INVALID, "%s: operands must be 4-element aligned with ld %% 4 == 0", fn);
+  float* part = static_cast<float*>(workspace);
+  int nblk = 0, DP = 256, RG = 1, rc;
   if (gramt_supported(m, k, n) && gramt_aligned(g1, ldg1) && gramt_aligned(g2, ldg2) && gramt_aligned(z, ldz) &&
       gramt_aligned(b, ldb)) {                          // the operand formed in LDS from DMA-streamed tiles (csrc/gramx.hip)
-    int nb = 0;
-    float* part = static_cast<float*>(workspace);
-    int rc = gramt_bn(g1, ldg1, g2, ldg2, z, ldz, mean, rstd, gamma, beta, relu, stats, inv_n, training, m, b, ldb, k, n, part,
-                      &nb, st);
-    if (rc != SGF_OK) return rc;
-    const int64_t len = static_cast<int64_t>(m) * k + m;
-    hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, part, nb, m, k, 256,
-                       1, c, ldc, colsum);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    rc = gramt_bn(g1, ldg1, g2, ldg2, z, ldz, mean, rstd, gamma, beta, relu, stats, inv_n, training, m, b, ldb, k, n, part,
+                  &nblk, st);
+  } else {
+    DP = padded_dim(m > k ? m : k);
+    ReduceArgs r = reduce_args(g1, ldg1, b, ldb, n, m, k, workspace);
+    r.a2 = g2; r.lda2 = ldg2; r.q = z; r.ldq = ldz;
+    r.bn_mean = mean; r.bn_rstd = rstd; r.bn_gamma = gamma; r.bn_beta = beta; r.bn_stats = stats; r.bn_inv_n = inv_n;
+    r.bn_training = training; r.bn_relu = relu;
+    rc = reduce_and_count<uint16_t, kModeGramBN>(r, DP, &nblk, &RG, st);
   }
-  const int DP = padded_dim(m > k ? m : k);
-  const int R = reduce_rows_per_tile<uint16_t, kModeGramBN>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  ReduceArgs r{};
-  r.a = g1; r.lda = ldg1; r.a2 = g2; r.lda2 = ldg2; r.q = z; r.ldq = ldz; r.b = b; r.ldb = ldb; r.den = nullptr;
-  r.n = n; r.d = m; r.db = k; r.heads = 1; r.b_heads = 1; r.gscale = 1.f;
-  r.bn_mean = mean; r.bn_rstd = rstd; r.bn_gamma = gamma; r.bn_beta = beta; r.bn_stats = stats; r.bn_inv_n = inv_n;
-  r.bn_training = training; r.bn_relu = relu;
-  r.partial = static_cast<float*>(workspace);
-  int rc = launch_reduce<uint16_t, kModeGramBN>(r, DP, nblk, st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<uint16_t, kModeGramBN>(DP);
-  const int64_t len = static_cast<int64_t>(m) * k + m;
-  hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, r.partial, nblk, m,
-                     k, DP, RG, c, ldc, colsum);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_gram(part, nblk, m, k, DP, RG, c, ldc, colsum, st);
 }
 
 // dW / db of a Linear whose output feeds a LayerNorm (+ activation), and the LayerNorm's own d gamma / d beta, WITHOUT a
@@ -1487,48 +1546,26 @@ extern "C" int sgf_gram_ln_bwd(const void* g, int64_t ldg, const void* xin, int6
               fn, m, k, dtype);
   SGF_REQUIRE(c && ldc >= k, SGF_E_INVALID, "%s: null c or ldc < k", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemset2DAsync(c, ldc * sizeof(float), 0, k * sizeof(float), m, st));
-    for (float* v : {colsum, dgamma, dbeta})
-      if (v) SGF_CHECK_HIP(hipMemsetAsync(v, 0, m * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_gram_outputs(c, ldc, m, k, {colsum, dgamma, dbeta}, st);
   SGF_REQUIRE(g && xin && b && mean && rstd, SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_gram_workspace_bytes(n, m, k), SGF_E_WORKSPACE, "%s: workspace too small", fn);
   SGF_REQUIRE(aligned4<uint16_t>(g, ldg) && aligned4<uint16_t>(xin, ldx) && aligned4<uint16_t>(b, ldb), SGF_E_INVALID,
               "%s: operands must be 4-element aligned with ld %% 4 == 0", fn);
+  float* part = static_cast<float*>(workspace);
+  int nblk = 0, DP = 256, RG = 1, rc;
   if (gramt_supported(m, k, n) && gramt_aligned(g, ldg) && gramt_aligned(xin, ldx) && gramt_aligned(b, ldb)) {   // csrc/gramx.hip
-    int nb = 0;
-    float* part = static_cast<float*>(workspace);
-    int rc = gramt_ln(g, ldg, xin, ldx, mean, rstd, gamma, beta, relu, m, b, ldb, k, n, part, &nb, st);
-    if (rc != SGF_OK) return rc;
-    const int64_t len = static_cast<int64_t>(m) * k + m;
-    hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, part, nb, m, k, 256,
-                       1, c, ldc, colsum);
-    if (dbeta) hipLaunchKernelGGL(k_vec_finalize, dim3((m + 31) / 32), dim3(256), 0, st, part, nb, kVecB, m, dbeta);
-    if (dgamma) hipLaunchKernelGGL(k_vec_finalize, dim3((m + 31) / 32), dim3(256), 0, st, part, nb, kVecC, m, dgamma);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    rc = gramt_ln(g, ldg, xin, ldx, mean, rstd, gamma, beta, relu, m, b, ldb, k, n, part, &nblk, st);
+  } else {
+    DP = m;                                            // a LayerNorm row = exactly one patch row of DP / 4 lanes
+    ReduceArgs r = reduce_args(g, ldg, b, ldb, n, m, k, workspace);
+    r.q = xin; r.ldq = ldx;
+    r.bn_mean = mean; r.bn_rstd = rstd; r.bn_gamma = gamma; r.bn_beta = beta; r.bn_relu = relu;
+    rc = reduce_and_count<uint16_t, kModeGramLN>(r, DP, &nblk, &RG, st);
   }
-  const int DP = m;                                    // a LayerNorm row = exactly one patch row of DP / 4 lanes
-  const int R = reduce_rows_per_tile<uint16_t, kModeGramLN>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  ReduceArgs r{};
-  r.a = g; r.lda = ldg; r.q = xin; r.ldq = ldx; r.b = b; r.ldb = ldb; r.den = nullptr;
-  r.n = n; r.d = m; r.db = k; r.heads = 1; r.b_heads = 1; r.gscale = 1.f;
-  r.bn_mean = mean; r.bn_rstd = rstd; r.bn_gamma = gamma; r.bn_beta = beta; r.bn_relu = relu;
-  r.partial = static_cast<float*>(workspace);
-  int rc = launch_reduce<uint16_t, kModeGramLN>(r, DP, nblk, st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<uint16_t, kModeGramLN>(DP);
-  const int64_t len = static_cast<int64_t>(m) * k + m;
-  hipLaunchKernelGGL(k_gram_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, r.partial, nblk, m,
-                     k, DP, RG, c, ldc, colsum);
-  if (dbeta) hipLaunchKernelGGL(k_vec_finalize, dim3((m + 31) / 32), dim3(256), 0, st, r.partial, nblk, kVecB, m, dbeta);
-  if (dgamma) hipLaunchKernelGGL(k_vec_finalize, dim3((m + 31) / 32), dim3(256), 0, st, r.partial, nblk, kVecC, m, dgamma);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  rc = finalize_gram(part, nblk, m, k, DP, RG, c, ldc, colsum, st);
+  if (rc != SGF_OK) return rc;
+  return finalize_ln_vectors(part, nblk, m, dbeta, dgamma, st);
 }
 
 // Two Gram products that share A in ONE paired launch (bf16 storage, m, k <= 256): c1 = a^T b1, c2 = a^T b2.
@@ -1536,15 +1573,14 @@ extern "C" int sgf_gram2(const void* a, int64_t lda, int32_t m, const void* b1, 
                          int32_t k, int64_t n, int32_t dtype, float* c1, int64_t ldc1, float* c2, int64_t ldc2,
                          float* colsum_a, void* workspace, size_t workspace_bytes, void* stream) {
   const char* fn = "sgf_gram2";
-  SGF_REQUIRE(n >= 0 && m >= 1 && k >= 1, SGF_E_INVALID, "%s: bad sizes n=%lld m=%d k=%d", fn, static_cast<long long>(n), m, k);
-  SGF_REQUIRE(m % 4 == 0 && k % 4 == 0, SGF_E_UNSUPPORTED, "%s: m and k must be multiples of 4 (m=%d k=%d)", fn, m, k);
-  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16 || dtype == SGF_F32_BF16X3, SGF_E_INVALID, "%s: unknown dtype %d", fn, dtype);
+  int rc = check_gram(fn, n, m, k, dtype);
+  if (rc != SGF_OK) return rc;
   SGF_REQUIRE(c1 && c2 && ldc1 >= k && ldc2 >= k, SGF_E_INVALID, "%s: null c or ldc < k", fn);
-  const int R = dtype == SGF_BF16 && m <= 256 && k <= 256
-                    ? reduce_rows_per_tile<uint16_t, kModeGram>(padded_dim(m > k ? m : k)) : 1;
-  const int64_t ntiles = (n + R - 1) / R;
-  if (dtype != SGF_BF16 || m > 256 || k > 256 || ntiles < 16) {     // nothing to pair: two plain products
-    int rc = sgf_gram(a, lda, m, b1, ldb1, k, n, dtype, c1, ldc1, colsum_a, workspace, workspace_bytes, stream);
+  const bool pairable = dtype == SGF_BF16 && m <= 256 && k <= 256;
+  const int DPr = padded_dim(m > k ? m : k);
+  const int nblk = pairable ? persistent_blocks(n, reduce_rows_per_tile<uint16_t, kModeGram>(DPr)) : 0;   // of one plain launch
+  if (nblk < 16) {                                                   // nothing to pair: two plain products
+    rc = sgf_gram(a, lda, m, b1, ldb1, k, n, dtype, c1, ldc1, colsum_a, workspace, workspace_bytes, stream);
     if (rc != SGF_OK) return rc;
     return sgf_gram(a, lda, m, b2, ldb2, k, n, dtype, c2, ldc2, nullptr, workspace, workspace_bytes, stream);
   }
@@ -1553,38 +1589,20 @@ extern "C" int sgf_gram2(const void* a, int64_t lda, int32_t m, const void* b1, 
   SGF_REQUIRE(aligned4<uint16_t>(a, lda) && aligned4<uint16_t>(b1, ldb1) && aligned4<uint16_t>(b2, ldb2), SGF_E_INVALID,
               "%s: a / b must be 4-element aligned with ld %% 4 == 0", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  int np = 0, DP = 256, RG = 1;
   if (gramx_supported(a, lda, m, b1, ldb1, k, n) && gramx_supported(a, lda, m, b2, ldb2, k, n)) {   // csrc/gramx.hip
-    int np = 0;
-    float* part = static_cast<float*>(workspace);
-    int rc = gramx_gram(a, lda, m, b1, ldb1, b2, ldb2, k, n, part, &np, st);
-    if (rc != SGF_OK) return rc;
-    const int64_t len = static_cast<int64_t>(m) * k + m;
-    const unsigned fb = static_cast<unsigned>((kFinChains * len + 255) / 256);
-    hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, part, np, m, k, 256, 1, c1, ldc1, colsum_a);
-    hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, part + static_cast<int64_t>(np) * kPartialStride, np, m, k,
-                       256, 1, c2, ldc2, static_cast<float*>(nullptr));
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    rc = gramx_gram(a, lda, m, b1, ldb1, b2, ldb2, k, n, part, &np, st);
+  } else {
+    DP = DPr;
+    RG = reduce_row_groups<uint16_t, kModeGram>(DP);
+    np = nblk / 2 / 8 * 8;                             // whole groups of 8 pairs = 16 consecutive blocks (>= 8: nblk >= 16)
+    ReduceArgs r = reduce_args(a, lda, b1, ldb1, n, m, k, workspace);
+    r.b2 = b2; r.ldb2 = ldb2; r.pair = 1;
+    rc = launch_reduce<uint16_t, kModeGram>(r, DP, 2 * np, st);
   }
-  const int DP = padded_dim(m > k ? m : k);
-  int64_t pairs = ntiles / 2 < kMaxBlocks / 2 ? ntiles / 2 : kMaxBlocks / 2;
-  pairs = pairs / 8 * 8;                               // whole groups of 8 pairs = 16 consecutive blocks (>= 8: ntiles >= 16)
-  ReduceArgs r{};
-  r.a = a; r.lda = lda; r.b = b1; r.ldb = ldb1; r.b2 = b2; r.ldb2 = ldb2; r.pair = 1;
-  r.q = nullptr; r.ldq = 0; r.den = nullptr;
-  r.n = n; r.d = m; r.db = k; r.heads = 1; r.b_heads = 1; r.gscale = 1.f;
-  r.partial = static_cast<float*>(workspace);
-  int rc = launch_reduce<uint16_t, kModeGram>(r, DP, static_cast<int>(2 * pairs), st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<uint16_t, kModeGram>(DP);
-  const int64_t len = static_cast<int64_t>(m) * k + m;
-  const unsigned fb = static_cast<unsigned>((kFinChains * len + 255) / 256);
-  hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, r.partial, static_cast<int>(pairs), m, k, DP, RG, c1, ldc1,
-                     colsum_a);
-  hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, r.partial + pairs * kPartialStride, static_cast<int>(pairs),
-                     m, k, DP, RG, c2, ldc2, static_cast<float*>(nullptr));
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_gram_pair(part, np, m, k, DP, RG, c1, ldc1, colsum_a, c2, ldc2, st);
 }
 
 extern "C" int32_t sgf_gram2_bn_bwd_supported(int32_t m, int32_t k, int64_t n, int32_t dtype) {
@@ -1612,13 +1630,7 @@ extern "C" int sgf_gram2_bn_bwd(const void* g, int64_t ldg, const void* z, int64
   int rc = gramb2(g, ldg, z, ldz, mean, rstd, gamma, beta, relu, stats, inv_n, training, m, b1, ldb1, b2, ldb2, k, n, dz, lddz,
                   part, &np, st);
   if (rc != SGF_OK) return rc;
-  const int64_t len = static_cast<int64_t>(m) * k + m;
-  const unsigned fb = static_cast<unsigned>((kFinChains * len + 255) / 256);
-  hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, part, np, m, k, 256, 1, c1, ldc1, colsum);
-  hipLaunchKernelGGL(k_gram_finalize, dim3(fb), dim3(256), 0, st, part + static_cast<int64_t>(np) * kPartialStride, np, m, k, 256,
-                     1, c2, ldc2, static_cast<float*>(nullptr));
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_gram_pair(part, np, m, k, 256, 1, c1, ldc1, colsum, c2, ldc2, st);
 }
 
 extern "C" size_t sgf_gram_workspace_bytes(int64_t n, int32_t m, int32_t k) {
@@ -1629,25 +1641,17 @@ extern "C" size_t sgf_gram_workspace_bytes(int64_t n, int32_t m, int32_t k) {
 extern "C" int sgf_gram(const void* a, int64_t lda, int32_t m, const void* b, int64_t ldb, int32_t k,
                         int64_t n, int32_t dtype, float* c, int64_t ldc, float* colsum_a,
                         void* workspace, size_t workspace_bytes, void* stream) {
-  SGF_REQUIRE(n >= 0 && m >= 1 && k >= 1, SGF_E_INVALID, "sgf_gram: bad sizes n=%lld m=%d k=%d",
-              static_cast<long long>(n), m, k);
-  SGF_REQUIRE(m % 4 == 0 && k % 4 == 0, SGF_E_UNSUPPORTED,
-              "sgf_gram: m and k must be multiples of 4 (m=%d k=%d)", m, k);
-  SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16 || dtype == SGF_F32_BF16X3, SGF_E_INVALID, "sgf_gram: unknown dtype %d",
-              dtype);
+  int rc = check_gram("sgf_gram", n, m, k, dtype);
+  if (rc != SGF_OK) return rc;
   SGF_REQUIRE(c && ldc >= k, SGF_E_INVALID, "sgf_gram: null c or ldc < k");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemset2DAsync(c, ldc * sizeof(float), 0, k * sizeof(float), m, st));
-    if (colsum_a) SGF_CHECK_HIP(hipMemsetAsync(colsum_a, 0, m * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_gram_outputs(c, ldc, m, k, {colsum_a}, st);
   SGF_REQUIRE(a && b, SGF_E_INVALID, "sgf_gram: null operand");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_gram_workspace_bytes(n, m, k), SGF_E_WORKSPACE,
               "sgf_gram: workspace too small");
-  if (dtype == SGF_F32 || dtype == SGF_F32_BF16X3)
-    return gram_t<float>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st, dtype == SGF_F32_BF16X3);
-  return gram_t<uint16_t>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st);
+  return by_dtype(f32_storage(dtype) ? SGF_F32 : dtype, [&](auto t) {
+    return gram_t<decltype(t)>(a, lda, m, b, ldb, k, n, c, ldc, colsum_a, workspace, st, dtype == SGF_F32_BF16X3);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1663,35 +1667,22 @@ int h_fwd_t(const void* h, int64_t ldh, int64_t n, int d, const float* M, const 
   ApplyArgs a{};
   a.a = h; a.lda = ldh;
   a.out = out; a.ldo = ldo;
-  a.bmat = M; a.trans_b = 0; a.cvec = m; a.dvec = w; a.beta = beta;
-  a.den = den; a.n = n; a.d = d; a.heads = 1; a.gscale = 1.f; a.accumulate = 0;
+  a.bmat = M; a.cvec = m; a.dvec = w; a.beta = beta;
+  a.den = den; a.n = n; a.d = d; a.heads = 1; a.gscale = 1.f;
   return launch_apply<T, kApplyHFwd>(a, padded_dim(d), st);
 }
 
+// the reduce alone: *nblk partials of geometry (*DP, *RG) for finalize_hstats
 template <typename T>
 int h_bwd_reduce_t(const void* h, int64_t ldh, const void* g, int64_t ldg, const void* o, int64_t ldo,
-                   const float* den, int64_t n, int d, float* hstats, void* ws, hipStream_t st) {
+                   const float* den, int64_t n, int d, void* ws, int* nblk, int* DP, int* RG, hipStream_t st) {
   SGF_REQUIRE(aligned4<T>(h, ldh) && aligned4<T>(g, ldg) && aligned4<T>(o, ldo), SGF_E_INVALID,
               "sgf_attn_h_bwd_reduce: h/g/o must be 4-element aligned with ld %% 4 == 0");
-  const int DP = padded_dim(d);
-  const int R = reduce_rows_per_tile<T, kModeBwdH>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  ReduceArgs a{};
-  a.a = h; a.lda = ldh;
-  a.b = g; a.ldb = ldg;
+  *DP = padded_dim(d);
+  ReduceArgs a = reduce_args(h, ldh, g, ldg, n, d, d, ws);
   a.q = o; a.ldq = ldo;
   a.den = den;
-  a.n = n; a.d = d; a.db = d; a.heads = 1; a.b_heads = 1; a.gscale = 1.f;
-  a.partial = static_cast<float*>(ws);
-  int rc = launch_reduce<T, kModeBwdH>(a, DP, nblk, st);
-  if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<T, kModeBwdH>(DP);
-  const int64_t len = sgf_attn_h_bstats_len(d);
-  hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st,
-                     a.partial, nblk, d, DP, RG, hstats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return reduce_and_count<T, kModeBwdH>(a, *DP, nblk, RG, st);
 }
 
 template <typename T>
@@ -1729,11 +1720,10 @@ extern "C" int sgf_attn_h_fwd(const void* h, int64_t ldh, int64_t n, int32_t d, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == SGF_F32_BF16X3)
     return attn_h_f32x_fwd(static_cast<const float*>(h), ldh, n, d, M, m, w, beta, static_cast<float*>(out), ldo, den, st);
-  if (dtype == SGF_F32) return h_fwd_t<float>(h, ldh, n, d, M, m, w, beta, out, ldo, den, st);
   // bf16, d in {64, 128, 256}, 16-byte aligned rows: the per-wave streaming kernel of csrc/rowgemm.hip
   if (hrow_supported(d, dtype, h, ldh, nullptr, 0, nullptr, 0, out, ldo) && reinterpret_cast<uintptr_t>(den) % 16 == 0)
     return hrow_fwd(h, ldh, n, d, M, m, w, beta, out, ldo, den, st);
-  return h_fwd_t<uint16_t>(h, ldh, n, d, M, m, w, beta, out, ldo, den, st);
+  return by_dtype(dtype, [&](auto t) { return h_fwd_t<decltype(t)>(h, ldh, n, d, M, m, w, beta, out, ldo, den, st); });
 }
 
 extern "C" int sgf_attn_h_bwd_reduce(const void* h, int64_t ldh, const void* g, int64_t ldg,
@@ -1744,27 +1734,22 @@ extern "C" int sgf_attn_h_bwd_reduce(const void* h, int64_t ldh, const void* g, 
   if (rc != SGF_OK) return rc;
   SGF_REQUIRE(hstats, SGF_E_INVALID, "sgf_attn_h_bwd_reduce: null hstats");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(hstats, 0, sgf_attn_h_bstats_len(d) * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_floats(hstats, sgf_attn_h_bstats_len(d), st);
   SGF_REQUIRE(h && g && o && den, SGF_E_INVALID, "sgf_attn_h_bwd_reduce: null pointer");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_attn_workspace_bytes(n, 1, d), SGF_E_WORKSPACE,
               "sgf_attn_h_bwd_reduce: workspace too small");
+  float* part = static_cast<float*>(workspace);
+  int nblk = 0, DP = 0, RG = 0;
   if (dtype == SGF_F32_BF16X3) {
-    int nb = 0, DP = 0, RG = 0;
     rc = attn_h_f32x_bwd_reduce(static_cast<const float*>(h), ldh, static_cast<const float*>(g), ldg,
-                                static_cast<const float*>(o), ldo, den, n, d, static_cast<float*>(workspace), &nb, &DP, &RG, st);
-    if (rc != SGF_OK) return rc;
-    const int64_t len = sgf_attn_h_bstats_len(d);
-    hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st,
-                       static_cast<const float*>(workspace), nb, d, DP, RG, hstats);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+                                static_cast<const float*>(o), ldo, den, n, d, part, &nblk, &DP, &RG, st);
+  } else {
+    rc = by_dtype(dtype, [&](auto t) {
+      return h_bwd_reduce_t<decltype(t)>(h, ldh, g, ldg, o, ldo, den, n, d, workspace, &nblk, &DP, &RG, st);
+    });
   }
-  if (dtype == SGF_F32)
-    return h_bwd_reduce_t<float>(h, ldh, g, ldg, o, ldo, den, n, d, hstats, workspace, st);
-  return h_bwd_reduce_t<uint16_t>(h, ldh, g, ldg, o, ldo, den, n, d, hstats, workspace, st);
+  if (rc != SGF_OK) return rc;
+  return finalize_hstats(part, nblk, d, DP, RG, hstats, st);
 }
 
 extern "C" int sgf_attn_h_bwd_apply(const void* h, int64_t ldh, const void* g, int64_t ldg,
@@ -1781,15 +1766,15 @@ extern "C" int sgf_attn_h_bwd_apply(const void* h, int64_t ldh, const void* g, i
   if (dtype == SGF_F32_BF16X3)
     return attn_h_f32x_bwd_apply(static_cast<const float*>(h), ldh, static_cast<const float*>(g), ldg,
                                  static_cast<const float*>(o), ldo, den, n, d, M, w, D, ds, static_cast<float*>(dh), lddh, st);
-  if (dtype == SGF_F32)
-    return h_bwd_apply_t<float>(h, ldh, g, ldg, o, ldo, den, n, d, M, w, D, ds, dh, lddh, st);
-  if (hrow_supported(d, dtype, h, ldh, g, ldg, o, ldo, dh, lddh)) {
+  if (hrow_supported(d, dtype, h, ldh, g, ldg, o, ldo, dh, lddh)) {      // bf16 only
     SGF_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0 &&
                     workspace_bytes >= hrow_partial_bytes(n, d),
                 SGF_E_WORKSPACE, "sgf_attn_h_bwd_apply: workspace %zu < %zu", workspace_bytes, hrow_partial_bytes(n, d));
     return hrow_bwd(h, ldh, g, ldg, o, ldo, den, n, d, M, w, D, ds, dh, lddh, workspace, st);
   }
-  return h_bwd_apply_t<uint16_t>(h, ldh, g, ldg, o, ldo, den, n, d, M, w, D, ds, dh, lddh, st);
+  return by_dtype(dtype, [&](auto t) {
+    return h_bwd_apply_t<decltype(t)>(h, ldh, g, ldg, o, ldo, den, n, d, M, w, D, ds, dh, lddh, st);
+  });
 }
 
 extern "C" size_t sgf_attn_h_bwd_apply_workspace_bytes(int64_t n, int32_t d, int32_t dtype) {
@@ -1833,43 +1818,24 @@ extern "C" int sgf_attn_h_bwd_reduce_scaled(const void* h, int64_t ldh, const vo
   SGF_REQUIRE(dtype == SGF_BF16, SGF_E_UNSUPPORTED, "sgf_attn_h_bwd_reduce_scaled: bf16 storage only");
   SGF_REQUIRE(hstats, SGF_E_INVALID, "sgf_attn_h_bwd_reduce_scaled: null hstats");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(hstats, 0, sgf_attn_h_bstats_len(d) * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_floats(hstats, sgf_attn_h_bstats_len(d), st);
   SGF_REQUIRE(h && g && rowscal, SGF_E_INVALID, "sgf_attn_h_bwd_reduce_scaled: null pointer");
   SGF_REQUIRE(aligned4<uint16_t>(h, ldh) && aligned4<uint16_t>(g, ldg) && reinterpret_cast<uintptr_t>(rowscal) % 8 == 0,
               SGF_E_INVALID, "sgf_attn_h_bwd_reduce_scaled: h / g must be 4-element aligned with ld %% 4 == 0");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_attn_workspace_bytes(n, 1, d), SGF_E_WORKSPACE,
               "sgf_attn_h_bwd_reduce_scaled: workspace too small");
+  float* part = static_cast<float*>(workspace);
+  int nblk = 0, DP = 256, RG = 1;
   if (gramx_supported(h, ldh, d, g, ldg, d, n)) {       // csrc/gramx.hip
-    int nb = 0;
-    rc = gramx_bwdhs(h, ldh, g, ldg, rowscal, d, n, static_cast<float*>(workspace), &nb, st);
-    if (rc != SGF_OK) return rc;
-    const int64_t len = sgf_attn_h_bstats_len(d);
-    hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st,
-                       static_cast<const float*>(workspace), nb, d, 256, 1, hstats);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    rc = gramx_bwdhs(h, ldh, g, ldg, rowscal, d, n, part, &nblk, st);
+  } else {
+    DP = padded_dim(d);
+    ReduceArgs a = reduce_args(h, ldh, g, ldg, n, d, d, workspace);
+    a.den = rowscal;
+    rc = reduce_and_count<uint16_t, kModeBwdHS>(a, DP, &nblk, &RG, st);
   }
-  const int DP = padded_dim(d);
-  const int R = reduce_rows_per_tile<uint16_t, kModeBwdHS>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  ReduceArgs a{};
-  a.a = h; a.lda = ldh;
-  a.b = g; a.ldb = ldg;
-  a.den = rowscal;
-  a.n = n; a.d = d; a.db = d; a.heads = 1; a.b_heads = 1; a.gscale = 1.f;
-  a.partial = static_cast<float*>(workspace);
-  rc = launch_reduce<uint16_t, kModeBwdHS>(a, DP, nblk, st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<uint16_t, kModeBwdHS>(DP);
-  const int64_t len = sgf_attn_h_bstats_len(d);
-  hipLaunchKernelGGL(k_hbwd_finalize, dim3(static_cast<unsigned>((kFinChains * len + 255) / 256)), dim3(256), 0, st, a.partial, nblk, d,
-                     DP, RG, hstats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_hstats(part, nblk, d, DP, RG, hstats, st);
 }
 
 extern "C" int sgf_attn_h_bwd_post(const void* h, int64_t ldh, int64_t n, int32_t d, int32_t dtype, const float* D,
@@ -1896,13 +1862,14 @@ extern "C" int32_t sgf_attn_max_blocks(void) { return kMaxBlocks; }
 extern "C" int32_t sgf_attn_tile_rows(int32_t kind, int32_t d, int32_t dtype) {
   if (d < 1 || d > 256 || (dtype != SGF_F32 && dtype != SGF_BF16) || (kind != 0 && kind != 1)) return -1;
   const int DP = padded_dim(d);
-  if (kind == 1) return dtype == SGF_F32 ? apply_rows_per_tile<float>(DP) : apply_rows_per_tile<uint16_t>(DP);
-  // every reduce mode of one storage type walks the same tile height (the bf16 wave count differs, the rows do not)
-  const int r = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeFwd>(DP) : reduce_rows_per_tile<uint16_t, kModeFwd>(DP);
-  const int rb = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeBwd>(DP) : reduce_rows_per_tile<uint16_t, kModeBwd>(DP);
-  const int rh = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeBwdH>(DP) : reduce_rows_per_tile<uint16_t, kModeBwdH>(DP);
-  const int rg = dtype == SGF_F32 ? reduce_rows_per_tile<float, kModeGram>(DP) : reduce_rows_per_tile<uint16_t, kModeGram>(DP);
-  return (r == rb && r == rh && r == rg) ? r : -1;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (kind == 1) return apply_rows_per_tile<T>(DP);
+    // every reduce mode of one storage type walks the same tile height (the bf16 wave count differs, the rows do not)
+    const int r = reduce_rows_per_tile<T, kModeFwd>(DP);
+    return (r == reduce_rows_per_tile<T, kModeBwd>(DP) && r == reduce_rows_per_tile<T, kModeBwdH>(DP) &&
+            r == reduce_rows_per_tile<T, kModeGram>(DP)) ? r : -1;
+  });
 }
 
 extern "C" int64_t sgf_attn_stats_len(int32_t heads, int32_t d) {
@@ -1924,30 +1891,15 @@ int fwd_reduce_t(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
                  int64_t n, int heads, int v_heads, int d, float* stats, void* ws, hipStream_t st) {
   SGF_REQUIRE(aligned4<T>(q, ldq) && aligned4<T>(k, ldk) && aligned4<T>(v, ldv), SGF_E_INVALID,
               "sgf_attn_fwd_reduce: q/k/v must be 4-element aligned with ld %% 4 == 0");
+  if (n == 0) return zero_floats(stats, sgf_attn_stats_len(heads, d), st);
   const int DP = padded_dim(d);
-  const int R = reduce_rows_per_tile<T, kModeFwd>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  const int64_t len = sgf_attn_stats_len(heads, d);
-  if (nblk == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(stats, 0, len * sizeof(float), st));
-    return SGF_OK;
-  }
-  ReduceArgs a{};
-  a.a = k; a.lda = ldk;
-  a.b = v; a.ldb = ldv;
+  ReduceArgs a = reduce_args(k, ldk, v, ldv, n, d, d, ws);
   a.q = q; a.ldq = ldq;
-  a.den = nullptr;
-  a.n = n; a.d = d; a.db = d; a.heads = heads; a.b_heads = v_heads; a.gscale = 1.f;
-  a.partial = static_cast<float*>(ws);
-  int rc = launch_reduce<T, kModeFwd>(a, DP, nblk, st);
+  a.heads = heads; a.b_heads = v_heads;
+  int nblk = 0, RG = 0;
+  int rc = reduce_and_count<T, kModeFwd>(a, DP, &nblk, &RG, st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<T, kModeFwd>(DP);
-  const int fb = static_cast<int>((len + 255) / 256);
-  hipLaunchKernelGGL(k_attn_finalize, dim3(fb), dim3(256), 0, st, a.partial, nblk, heads, d, DP, RG,
-                     kModeFwd, stats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_attn(a.partial, nblk, heads, d, DP, RG, kModeFwd, stats, st);
 }
 
 template <typename T>
@@ -1967,10 +1919,9 @@ int fwd_apply_t(const void* q, int64_t ldq, const void* v, int64_t ldv, int64_t 
     a.bmat = stats + static_cast<int64_t>(h) * d * d;
     a.cvec = stats + static_cast<int64_t>(heads) * d * d + static_cast<int64_t>(h) * d;
     a.den = den + h;
-    a.stats = stats; a.stats_len = slen; a.sdot = nullptr;
+    a.stats = stats; a.stats_len = slen;
     a.n = n; a.d = d; a.heads = heads;
     a.ntot = static_cast<float>(n_total); a.gscale = 1.f / heads;
-    a.trans_b = 0; a.accumulate = 0;
     int rc = launch_apply<T, kApplyFwd>(a, DP, st);
     if (rc != SGF_OK) return rc;
   }
@@ -1983,48 +1934,32 @@ int fwd_apply_t(const void* q, int64_t ldq, const void* v, int64_t ldv, int64_t 
   return SGF_OK;
 }
 
+// g is [n, d], the gradient of the head MEAN shared by all heads (it enters with 1/H) — or [n, H, d] (g_per_head)
 template <typename T>
-int bwd_reduce_t(const void* q, int64_t ldq, const void* g, int64_t ldg, const void* o, int64_t ldo,
-                 const float* den, int64_t n, int heads, int d, float* bstats, void* ws,
-                 hipStream_t st, bool g_per_head = false) {
+int bwd_reduce_t(const char* fn, bool g_per_head, const void* q, int64_t ldq, const void* g, int64_t ldg, const void* o,
+                 int64_t ldo, const float* den, int64_t n, int heads, int d, float* bstats, void* ws, hipStream_t st) {
   SGF_REQUIRE(aligned4<T>(q, ldq) && aligned4<T>(g, ldg) && aligned4<T>(o, ldo), SGF_E_INVALID,
-              "sgf_attn_bwd_reduce: q/g/o must be 4-element aligned with ld %% 4 == 0");
+              "%s: q/g/o must be 4-element aligned with ld %% 4 == 0", fn);
+  if (n == 0) return zero_floats(bstats, sgf_attn_bstats_len(heads, d), st);
   const int DP = padded_dim(d);
-  const int R = reduce_rows_per_tile<T, kModeBwd>(DP);
-  const int64_t ntiles = (n + R - 1) / R;
-  const int nblk = static_cast<int>(ntiles < kMaxBlocks ? ntiles : kMaxBlocks);
-  const int64_t len = sgf_attn_bstats_len(heads, d);
-  if (nblk == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(bstats, 0, len * sizeof(float), st));
-    return SGF_OK;
-  }
-  ReduceArgs a{};
-  a.a = q; a.lda = ldq;
-  a.b = g; a.ldb = ldg;     // g is [n, d]: the gradient of the head MEAN, shared by all heads — or [n, H, d] (g_per_head)
+  ReduceArgs a = reduce_args(q, ldq, g, ldg, n, d, d, ws);
   a.q = o; a.ldq = ldo;     // o is [n, H, d] (or out when H == 1)
   a.den = den;
-  a.n = n; a.d = d; a.db = d; a.heads = heads;
-  a.b_heads = g_per_head ? heads : 1; a.gscale = g_per_head ? 1.f : 1.f / heads;
-  a.partial = static_cast<float*>(ws);
-  int rc = launch_reduce<T, kModeBwd>(a, DP, nblk, st);
+  a.heads = heads; a.b_heads = g_per_head ? heads : 1; a.gscale = g_per_head ? 1.f : 1.f / heads;
+  int nblk = 0, RG = 0;
+  int rc = reduce_and_count<T, kModeBwd>(a, DP, &nblk, &RG, st);
   if (rc != SGF_OK) return rc;
-  const int RG = reduce_row_groups<T, kModeBwd>(DP);
-  const int fb = static_cast<int>((len + 1 + 255) / 256);
-  hipLaunchKernelGGL(k_attn_finalize, dim3(fb), dim3(256), 0, st, a.partial, nblk, heads, d, DP, RG,
-                     kModeBwd, bstats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return finalize_attn(a.partial, nblk, heads, d, DP, RG, kModeBwd, bstats, st);
 }
 
 template <typename T>
-int bwd_apply_t(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den, int64_t n,
+int bwd_apply_t(const char* fn, bool g_per_head, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                int64_t ldv, const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den, int64_t n,
                 double n_total, int heads, int v_heads, int d, const float* stats, float* bstats,
-                void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
-                hipStream_t st, bool g_per_head = false) {
+                void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, hipStream_t st) {
   SGF_REQUIRE(aligned4<T>(q, ldq) && aligned4<T>(k, ldk) && aligned4<T>(v, ldv) &&
                   aligned4<T>(g, ldg) && aligned4<T>(o, ldo),
-              SGF_E_INVALID, "sgf_attn_bwd_apply: operands must be 4-element aligned");
+              SGF_E_INVALID, "%s: operands must be 4-element aligned", fn);
   if (n == 0) return SGF_OK;
   const int DP = padded_dim(d);
   const int64_t slen = sgf_attn_stats_len(heads, d);
@@ -2071,6 +2006,7 @@ int bwd_apply_t(const void* q, int64_t ldq, const void* k, int64_t ldk, const vo
   }
   return SGF_OK;
 }
+
 }  // namespace
 
 extern "C" int sgf_attn_fwd_reduce(const void* q, int64_t ldq, const void* k, int64_t ldk,
@@ -2085,9 +2021,9 @@ extern "C" int sgf_attn_fwd_reduce(const void* q, int64_t ldq, const void* k, in
   SGF_REQUIRE(workspace_bytes >= sgf_attn_workspace_bytes(n, heads, d) && workspace, SGF_E_WORKSPACE,
               "sgf_attn_fwd_reduce: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return fwd_reduce_t<float>(q, ldq, k, ldk, v, ldv, n, heads, v_heads, d, stats, workspace, st);
-  return fwd_reduce_t<uint16_t>(q, ldq, k, ldk, v, ldv, n, heads, v_heads, d, stats, workspace, st);
+  return by_dtype(dtype, [&](auto t) {
+    return fwd_reduce_t<decltype(t)>(q, ldq, k, ldk, v, ldv, n, heads, v_heads, d, stats, workspace, st);
+  });
 }
 
 extern "C" int sgf_attn_fwd_apply(const void* q, int64_t ldq, const void* v, int64_t ldv, int64_t n,
@@ -2103,27 +2039,52 @@ extern "C" int sgf_attn_fwd_apply(const void* q, int64_t ldq, const void* v, int
   SGF_REQUIRE(heads == 1 || o_heads || n == 0, SGF_E_INVALID,
               "sgf_attn_fwd_apply: o_heads required when heads > 1");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return fwd_apply_t<float>(q, ldq, v, ldv, n, n_total, heads, v_heads, d, stats, out, ldo, den,
-                              o_heads, st);
-  return fwd_apply_t<uint16_t>(q, ldq, v, ldv, n, n_total, heads, v_heads, d, stats, out, ldo, den,
-                               o_heads, st);
+  return by_dtype(dtype, [&](auto t) {
+    return fwd_apply_t<decltype(t)>(q, ldq, v, ldv, n, n_total, heads, v_heads, d, stats, out, ldo, den, o_heads, st);
+  });
 }
+
+namespace {
+// sgf_attn_bwd_reduce (g_per_head = false) and sgf_attn_bwd_reduce_heads (true, ldg >= H * d) under the name `fn`
+int attn_bwd_reduce(const char* fn, bool g_per_head, const void* q, int64_t ldq, const void* g, int64_t ldg, const void* o,
+                    int64_t ldo, const float* den, int64_t n, int heads, int d, int dtype, float* bstats, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  int rc = check_common(fn, n, heads, d, dtype);
+  if (rc != SGF_OK) return rc;
+  SGF_REQUIRE(bstats && (n == 0 || (q && g && o && den)), SGF_E_INVALID, "%s: null pointer", fn);
+  SGF_REQUIRE(!g_per_head || n == 0 || ldg >= static_cast<int64_t>(heads) * d, SGF_E_INVALID, "%s: ldg < H * d", fn);
+  SGF_REQUIRE(workspace_bytes >= sgf_attn_workspace_bytes(n, heads, d) && workspace, SGF_E_WORKSPACE,
+              "%s: workspace too small", fn);
+  return by_dtype(dtype, [&](auto t) {
+    return bwd_reduce_t<decltype(t)>(fn, g_per_head, q, ldq, g, ldg, o, ldo, den, n, heads, d, bstats, workspace,
+                                     static_cast<hipStream_t>(stream));
+  });
+}
+
+// sgf_attn_bwd_apply and sgf_attn_bwd_apply_heads, likewise
+int attn_bwd_apply(const char* fn, bool g_per_head, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                   int64_t ldv, const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den, int64_t n,
+                   double n_total, int heads, int v_heads, int d, int dtype, const float* stats, float* bstats, void* dq,
+                   int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv, void* stream) {
+  int rc = check_common(fn, n, heads, d, dtype);
+  if (rc != SGF_OK) return rc;
+  SGF_REQUIRE(v_heads == heads || v_heads == 1, SGF_E_INVALID, "%s: v_heads must be H or 1", fn);
+  SGF_REQUIRE(stats && bstats && (n == 0 || (q && k && v && g && o && den && dq && dk && dv)), SGF_E_INVALID,
+              "%s: null pointer", fn);
+  SGF_REQUIRE(!g_per_head || n == 0 || ldg >= static_cast<int64_t>(heads) * d, SGF_E_INVALID, "%s: ldg < H * d", fn);
+  return by_dtype(dtype, [&](auto t) {
+    return bwd_apply_t<decltype(t)>(fn, g_per_head, q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads, v_heads, d,
+                                    stats, bstats, dq, lddq, dk, lddk, dv, lddv, static_cast<hipStream_t>(stream));
+  });
+}
+}  // namespace
 
 extern "C" int sgf_attn_bwd_reduce(const void* q, int64_t ldq, const void* g, int64_t ldg,
                                    const void* o, int64_t ldo, const float* den, int64_t n,
                                    int32_t heads, int32_t d, int32_t dtype, float* bstats,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_common("sgf_attn_bwd_reduce", n, heads, d, dtype);
-  if (rc != SGF_OK) return rc;
-  SGF_REQUIRE(bstats && (n == 0 || (q && g && o && den)), SGF_E_INVALID,
-              "sgf_attn_bwd_reduce: null pointer");
-  SGF_REQUIRE(workspace_bytes >= sgf_attn_workspace_bytes(n, heads, d) && workspace, SGF_E_WORKSPACE,
-              "sgf_attn_bwd_reduce: workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return bwd_reduce_t<float>(q, ldq, g, ldg, o, ldo, den, n, heads, d, bstats, workspace, st);
-  return bwd_reduce_t<uint16_t>(q, ldq, g, ldg, o, ldo, den, n, heads, d, bstats, workspace, st);
+  return attn_bwd_reduce("sgf_attn_bwd_reduce", false, q, ldq, g, ldg, o, ldo, den, n, heads, d, dtype, bstats, workspace,
+                         workspace_bytes, stream);
 }
 
 extern "C" int sgf_attn_bwd_apply(const void* q, int64_t ldq, const void* k, int64_t ldk,
@@ -2133,18 +2094,8 @@ extern "C" int sgf_attn_bwd_apply(const void* q, int64_t ldq, const void* k, int
                                   int32_t dtype, const float* stats, float* bstats, void* dq,
                                   int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
                                   void* stream) {
-  int rc = check_common("sgf_attn_bwd_apply", n, heads, d, dtype);
-  if (rc != SGF_OK) return rc;
-  SGF_REQUIRE(v_heads == heads || v_heads == 1, SGF_E_INVALID,
-              "sgf_attn_bwd_apply: v_heads must be H or 1");
-  SGF_REQUIRE(stats && bstats && (n == 0 || (q && k && v && g && o && den && dq && dk && dv)),
-              SGF_E_INVALID, "sgf_attn_bwd_apply: null pointer");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return bwd_apply_t<float>(q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads,
-                              v_heads, d, stats, bstats, dq, lddq, dk, lddk, dv, lddv, st);
-  return bwd_apply_t<uint16_t>(q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads,
-                               v_heads, d, stats, bstats, dq, lddq, dk, lddk, dv, lddv, st);
+  return attn_bwd_apply("sgf_attn_bwd_apply", false, q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads, v_heads,
+                        d, dtype, stats, bstats, dq, lddq, dk, lddk, dv, lddv, stream);
 }
 
 // The same backward for PER-HEAD output gradients (full_attention_conv returns [N, H, D], medium/ours.py:14-46, 100M/ours.py:12-53):
@@ -2152,16 +2103,8 @@ extern "C" int sgf_attn_bwd_apply(const void* q, int64_t ldq, const void* k, int
 extern "C" int sgf_attn_bwd_reduce_heads(const void* q, int64_t ldq, const void* g, int64_t ldg, const void* o, int64_t ldo,
                                          const float* den, int64_t n, int32_t heads, int32_t d, int32_t dtype, float* bstats,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = check_common("sgf_attn_bwd_reduce_heads", n, heads, d, dtype);
-  if (rc != SGF_OK) return rc;
-  SGF_REQUIRE(bstats && (n == 0 || (q && g && o && den)), SGF_E_INVALID, "sgf_attn_bwd_reduce_heads: null pointer");
-  SGF_REQUIRE(n == 0 || ldg >= static_cast<int64_t>(heads) * d, SGF_E_INVALID, "sgf_attn_bwd_reduce_heads: ldg < H * d");
-  SGF_REQUIRE(workspace_bytes >= sgf_attn_workspace_bytes(n, heads, d) && workspace, SGF_E_WORKSPACE,
-              "sgf_attn_bwd_reduce_heads: workspace too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return bwd_reduce_t<float>(q, ldq, g, ldg, o, ldo, den, n, heads, d, bstats, workspace, st, true);
-  return bwd_reduce_t<uint16_t>(q, ldq, g, ldg, o, ldo, den, n, heads, d, bstats, workspace, st, true);
+  return attn_bwd_reduce("sgf_attn_bwd_reduce_heads", true, q, ldq, g, ldg, o, ldo, den, n, heads, d, dtype, bstats, workspace,
+                         workspace_bytes, stream);
 }
 
 extern "C" int sgf_attn_bwd_apply_heads(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
@@ -2169,16 +2112,6 @@ extern "C" int sgf_attn_bwd_apply_heads(const void* q, int64_t ldq, const void* 
                                         double n_total, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype,
                                         const float* stats, float* bstats, void* dq, int64_t lddq, void* dk, int64_t lddk,
                                         void* dv, int64_t lddv, void* stream) {
-  int rc = check_common("sgf_attn_bwd_apply_heads", n, heads, d, dtype);
-  if (rc != SGF_OK) return rc;
-  SGF_REQUIRE(v_heads == heads || v_heads == 1, SGF_E_INVALID, "sgf_attn_bwd_apply_heads: v_heads must be H or 1");
-  SGF_REQUIRE(stats && bstats && (n == 0 || (q && k && v && g && o && den && dq && dk && dv)), SGF_E_INVALID,
-              "sgf_attn_bwd_apply_heads: null pointer");
-  SGF_REQUIRE(n == 0 || ldg >= static_cast<int64_t>(heads) * d, SGF_E_INVALID, "sgf_attn_bwd_apply_heads: ldg < H * d");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return bwd_apply_t<float>(q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads, v_heads, d, stats, bstats, dq,
-                              lddq, dk, lddk, dv, lddv, st, true);
-  return bwd_apply_t<uint16_t>(q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads, v_heads, d, stats, bstats, dq,
-                               lddq, dk, lddk, dv, lddv, st, true);
+  return attn_bwd_apply("sgf_attn_bwd_apply_heads", true, q, ldq, k, ldk, v, ldv, g, ldg, o, ldo, den, n, n_total, heads,
+                        v_heads, d, dtype, stats, bstats, dq, lddq, dk, lddk, dv, lddv, stream);
 }
