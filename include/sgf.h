@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 661 /* 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 662 /* 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -174,6 +174,13 @@ int sgf_spmm(const int64_t* rowptr, const int32_t* colind, const float* val, con
  * such segments, sum over rows with len > long_len of ceil(len / segment_len), computed by the caller
  * once per CSR (0 = plain sgf_spmm).  Same result as sgf_spmm up to fp32 summation order. */
 int32_t sgf_spmm_segment_len(void);
+/* Which kernel the next sgf_spmm / sgf_spmm_split (stream = 0) or sgf_spmm_stream (stream = 1) launch with these operands
+ * would run, under the current (cached) SGF_SPMM_KERNEL — a host query, no GPU needed; it calls the launcher's own rule.
+ * aligned16: x and y are both 16-byte aligned.  Returns arm | lanes_per_row << 8 with arm 0 = k_spmm_seg_bf16x2 (the
+ * stream of bf16 row pairs), 1 = k_spmm_seg, 2 = k_spmm_row, 3 = k_spmm_wave, 4 = k_spmm_sub<lanes_per_row>;
+ * lanes_per_row is non-zero only for arm 4.  -1 for an unknown dtype. */
+int32_t sgf_spmm_arm(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols, int32_t aligned16,
+                     int32_t stream);
 size_t sgf_spmm_split_workspace_bytes(int64_t long_segments, int32_t d);
 int sgf_spmm_split(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x,
                    int64_t ldx, int64_t n_cols, void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype,
@@ -232,6 +239,12 @@ int sgf_spmm_plan(const int64_t* rowptr, const int32_t* colind, const float* val
                   int32_t* nlds, int32_t* sh_ptr, int32_t* sh_cols, int64_t* stats, void* workspace,
                   size_t workspace_bytes, void* stream);
 int32_t sgf_spmm_lds_rows_len(int32_t dtype);
+/* Which row-block kernel the next sgf_spmm_blocked launch with these operands would run, under the current (cached)
+ * SGF_SPMM_BLK2 (host query; the launcher's own rule): 0 = k_spmm_blk2 (bf16, two entries per instruction), 1 / 2 =
+ * k_spmm_blk in its lean / deep register budget.  aligned16: x and y both 16-byte aligned.  -1 for an unknown dtype or a
+ * rows_per_block / lds_rows that sgf_spmm_blocked rejects. */
+int32_t sgf_spmm_blocked_arm(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_rows, int32_t rows_per_block,
+                             int32_t lds_rows, int32_t aligned16);
 int sgf_spmm_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eval, const int32_t* nlds,
                      const int32_t* sh_ptr, const int32_t* sh_cols, const void* x, int64_t ldx, void* y,
                      int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, int32_t rows_per_block,

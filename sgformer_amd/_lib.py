@@ -44,6 +44,7 @@ SIGNATURES = {
     "sgf_graph_prologue_emit": (c_int32, [c_int64, c_int64, c_int32, c_int32, c_int64, _P, _P, c_size_t, _P]),
     "sgf_spmm": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, _P]),
     "sgf_spmm_segment_len": (c_int32, []),
+    "sgf_spmm_arm": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sgf_spmm_split_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_spmm_split": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int64,
                                  c_int64, _P, c_size_t, _P]),
@@ -55,6 +56,7 @@ SIGNATURES = {
     "sgf_spmm_plan": (c_int32, [_P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P, _P,
                                 _P, c_size_t, _P]),
     "sgf_spmm_lds_rows_len": (c_int32, [c_int32]),
+    "sgf_spmm_blocked_arm": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32]),
     "sgf_spmm_blocked": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32,
                                    c_int32, c_int32, c_int64, c_int64, _P, c_size_t, _P]),
     "sgf_spmm_tile_supported": (c_int32, [c_int32, c_int32]),

@@ -1118,28 +1118,58 @@ enum Forced { kForceNone = -1, kForceWave, kForceRow, kForceSeg, kForceSeg2, kFo
 const char* const kForcedWords[] = {"wave", "row", "seg", "seg2", "sub"};
 EnvWord g_forced{"SGF_SPMM_KERNEL", kForcedWords, 5};
 
+// Which row-block kernel serves sgf_spmm_blocked — the one rule, shared by launch_blocked and sgf_spmm_blocked_arm.
+//   Blk2: bf16 storage, d % 8 == 0 and <= 256, ldx / ldy multiples of 8, x / y 16-byte aligned (`aligned16`), X within 32-bit
+//         buffer offsets, at most 8 waves (64 rows) per block, SGF_SPMM_BLK2 != 0;
+//   otherwise k_spmm_blk in one of two register budgets: "deep" keeps 4 KiB of gathers + 8 LDS entries in flight per wave
+//         (<= 128 VGPRs, 16 waves per CU); "lean" halves both and fits 64 VGPRs, for block shapes of which the LDS admits
+//         more than 16 waves per CU.
+struct BlkChoice {
+  bool blk2, lean;      // lean: the register budget of k_spmm_blk for this block shape (known whether or not blk2 runs)
+  int threads;
+  size_t lds_bytes;     // staged rows (512 B bf16 / 1 KiB fp32 each, both kernels) + the waves' scratch: the launch's dynamic LDS
+  uint64_t x_bytes;     // n_rows * ldx * element size, the buffer bound of k_spmm_blk2
+};
+template <typename T> constexpr size_t blk_slot_bytes() { return 64 * sizeof(typename Stored<T>::type); }
+static_assert(blk_slot_bytes<uint16_t>() == 512, "k_spmm_blk2 lays a staged bf16 row out as 32 lanes x 16 bytes");
+BlkChoice choose_blocked(int32_t d, size_t elem_size, int64_t ldx, int64_t ldy, int64_t n_rows, int32_t rows_per_block,
+                         int32_t lds_rows, bool aligned16) {
+  BlkChoice c;
+  c.threads = rows_per_block / kBlkRowsPerWave * 64;
+  c.x_bytes = static_cast<uint64_t>(n_rows) * static_cast<uint64_t>(ldx) * elem_size;
+  c.lds_bytes = static_cast<size_t>(lds_rows) * (elem_size == 4 ? blk_slot_bytes<float>() : blk_slot_bytes<uint16_t>()) +
+                static_cast<size_t>(c.threads / 64) * kScratchPerWave;
+  const size_t per_cu = 160 * 1024;
+  c.lean = (per_cu / c.lds_bytes) * static_cast<size_t>(c.threads / 64) > 16;
+  c.blk2 = elem_size == 2 && d % 8 == 0 && d <= 256 && ldx % 8 == 0 && ldy % 8 == 0 && aligned16 &&
+           c.x_bytes < (static_cast<uint64_t>(1) << 32) && c.threads <= 512 && g_blk2.get() != 0;
+  return c;
+}
+// What sgf_spmm_blocked accepts as a block shape (sgf_spmm_blocked_arm answers -1 for anything else)
+bool blk_rows_ok(int32_t rows_per_block) {
+  return rows_per_block >= kBlkRowsPerWave && rows_per_block <= 128 && rows_per_block % kBlkRowsPerWave == 0;
+}
+bool blk_lds_rows_ok(int32_t lds_rows, int32_t dtype) { return lds_rows >= 1 && lds_rows <= sgf_spmm_lds_rows_len(dtype); }
+
 template <typename T>
 int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eval, const int32_t* nlds,
                    const int32_t* sh_ptr, const int32_t* sh_cols, const T* x, int64_t ldx, T* y, int64_t ldy,
                    int64_t n_rows, int32_t d, int32_t rows_per_block, int32_t lds_rows, hipStream_t st,
                    const LongQueue& lq, float* partial) {
-  using V = typename Stored<T>::type;
-  const int threads = rows_per_block / kBlkRowsPerWave * 64;
-  const size_t lds_bytes = static_cast<size_t>(lds_rows) * 64 * sizeof(V) +
-                           static_cast<size_t>(threads / 64) * kScratchPerWave;
+  const BlkChoice c = choose_blocked(d, sizeof(T), ldx, ldy, n_rows, rows_per_block, lds_rows,
+                                     reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0);
+  const int threads = c.threads;
+  const size_t lds_bytes = c.lds_bytes;
+  const bool lean = c.lean;
   const int64_t nb = (n_rows + rows_per_block - 1) / rows_per_block;
   // one XCD walks ~4096 consecutive rows at a time (its L2 then holds one neighbourhood, as in xcd_remap)
   int chunk = 4096 / rows_per_block;
   if (chunk < 1) chunk = 1;
-  // Two register budgets: "deep" keeps 4 KiB of gathers + 8 LDS entries in flight per wave (<= 128 VGPRs, 16 waves
-  // per CU); "lean" halves both and fits 64 VGPRs, for block shapes of which the LDS admits 32 waves per CU.
 #ifdef SGF_PROBES
   const int dbg = g_blk_debug.get();
 #else
   const int dbg = 0;
 #endif
-  const size_t per_cu = 160 * 1024;
-  const bool lean = (per_cu / lds_bytes) * static_cast<size_t>(threads / 64) > 16;
   constexpr int DGd = sizeof(T) == 4 ? 4 : 8, DGl = sizeof(T) == 4 ? 2 : 4;
   auto deep_fn = &k_spmm_blk<T, DGd, DGd, 4>;
   auto lean_fn = &k_spmm_blk<T, DGl, DGl, 8>;
@@ -1150,11 +1180,8 @@ int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eva
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
     attr_set[which] = lds_bytes;
   }
-  const uint64_t xb = static_cast<uint64_t>(n_rows) * static_cast<uint64_t>(ldx) * sizeof(T);
-  if (sizeof(T) == 2 && d % 8 == 0 && d <= 256 && ldx % 8 == 0 && ldy % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
-      reinterpret_cast<uintptr_t>(y) % 16 == 0 && xb < (static_cast<uint64_t>(1) << 32) && threads <= 512 &&
-      g_blk2.get() != 0) {
-    const size_t lds2 = static_cast<size_t>(lds_rows) * 512 + static_cast<size_t>(threads / 64) * kScratchPerWave;
+  if (c.blk2) {
+    const size_t lds2 = lds_bytes;   // (512-byte slots in both bf16 kernels: blk_slot_bytes)
     auto fn2 = &k_spmm_blk2<8, 4>;
     static thread_local size_t attr2 = 0;
     if (lds2 > attr2) {
@@ -1164,7 +1191,7 @@ int launch_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eva
     }
     hipLaunchKernelGGL(fn2, dim3(static_cast<unsigned>(nb)), dim3(threads), lds2, st, rowptr, ecode, eval, nlds, sh_ptr,
                        sh_cols, reinterpret_cast<const uint16_t*>(x), static_cast<uint32_t>(ldx * sizeof(T)),
-                       static_cast<uint32_t>(xb), reinterpret_cast<uint16_t*>(y), ldy, n_rows, d, rows_per_block,
+                       static_cast<uint32_t>(c.x_bytes), reinterpret_cast<uint16_t*>(y), ldy, n_rows, d, rows_per_block,
                        lds_rows, chunk, lq, dbg);
   } else if (lean)
     hipLaunchKernelGGL(lean_fn, dim3(static_cast<unsigned>(nb)), dim3(threads), lds_bytes, st, rowptr, ecode, eval,
@@ -1204,17 +1231,27 @@ Choice choose_kernel(int32_t d, size_t elem_size, bool fits32, bool pair_ok, boo
   return {Arm::Sub, d > 64 ? 32 : d > 32 ? 16 : d > 16 ? 8 : d > 8 ? 4 : d > 4 ? 2 : 1};
 }
 
+// choose_kernel for the operands of one launch under the current SGF_SPMM_KERNEL — shared by launch and sgf_spmm_arm.
+// `aligned16`: x and y both 16-byte aligned.
+Choice choose_for_operands(int32_t d, size_t elem_size, int64_t ldx, int64_t ldy, int64_t n_cols, bool aligned16,
+                           bool stream, uint64_t* x_bytes_out = nullptr) {
+  const uint64_t x_bytes = static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * elem_size;
+  if (x_bytes_out) *x_bytes_out = x_bytes;   // the buffer bound of the kernels that address x with 32-bit offsets
+  const bool fits32 = d <= 256 && n_cols > 0 && x_bytes < (static_cast<uint64_t>(1) << 32);
+  const bool pair_ok = d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && aligned16;
+  return choose_kernel(d, elem_size, fits32, pair_ok, stream, g_forced.get());
+}
+
 template <typename T>
 int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const T* x, int64_t ldx, int64_t n_cols,
            T* y, int64_t ldy, int64_t n_rows, int32_t d, hipStream_t st, const LongQueue& lq,
            float* partial, bool stream) {
   constexpr int UNROLL = 8;
   const dim3 block(kWavesPerBlock * 64);
-  const uint64_t x_bytes = static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * sizeof(T);
-  const bool fits32 = d <= 256 && n_cols > 0 && x_bytes < (static_cast<uint64_t>(1) << 32);
-  const bool pair_ok = d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
-                       reinterpret_cast<uintptr_t>(y) % 16 == 0;
-  const Choice c = choose_kernel(d, sizeof(T), fits32, pair_ok, stream, g_forced.get());
+  uint64_t x_bytes;
+  const Choice c = choose_for_operands(d, sizeof(T), ldx, ldy, n_cols,
+                                       reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0,
+                                       stream, &x_bytes);
   const int64_t nb = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;                              // a wave per row
   const int64_t nbs = (n_rows + kWavesPerBlock * kSegRows - 1) / (kWavesPerBlock * kSegRows);     // a wave per kSegRows rows
   const int chunk_rows = g_chunk_rows.get() > 0 ? g_chunk_rows.get() : 4096;   // one XCD walks ~4096 consecutive rows at a time
@@ -1331,6 +1368,13 @@ extern "C" int sgf_spmm(const int64_t* rowptr, const int32_t* colind, const floa
 
 extern "C" int32_t sgf_spmm_segment_len(void) { return kSegLen; }
 
+extern "C" int32_t sgf_spmm_arm(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols, int32_t aligned16,
+                                int32_t stream) {
+  if (dtype != SGF_F32 && dtype != SGF_BF16) return -1;
+  const Choice c = choose_for_operands(d, dtype == SGF_BF16 ? 2 : 4, ldx, ldy, n_cols, aligned16 != 0, stream != 0);
+  return static_cast<int32_t>(c.arm) | (c.arm == Arm::Sub ? c.lanes_per_row << 8 : 0);
+}
+
 extern "C" size_t sgf_spmm_split_workspace_bytes(int64_t long_segments, int32_t d) {
   if (long_segments < 0 || d < 0) return 0;
   return long_partial_off(long_segments) + static_cast<size_t>(long_segments) * static_cast<size_t>(d) * sizeof(float);
@@ -1390,6 +1434,14 @@ extern "C" int32_t sgf_spmm_lds_rows_len(int32_t dtype) {
   return dtype == SGF_BF16 ? 288 : 144;   // + 1 KiB of code / value scratch per wave = exactly 160 KiB at 16 waves
 }
 
+extern "C" int32_t sgf_spmm_blocked_arm(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_rows,
+                                        int32_t rows_per_block, int32_t lds_rows, int32_t aligned16) {
+  if (dtype != SGF_F32 && dtype != SGF_BF16) return -1;
+  if (!blk_rows_ok(rows_per_block) || !blk_lds_rows_ok(lds_rows, dtype)) return -1;   // (what sgf_spmm_blocked rejects)
+  const BlkChoice c = choose_blocked(d, dtype == SGF_BF16 ? 2 : 4, ldx, ldy, n_rows, rows_per_block, lds_rows, aligned16 != 0);
+  return c.blk2 ? 0 : c.lean ? 1 : 2;
+}
+
 extern "C" int sgf_spmm_blocked(const int64_t* rowptr, const int32_t* ecode, const float* eval,
                                 const int32_t* nlds, const int32_t* sh_ptr, const int32_t* sh_cols,
                                 const void* x, int64_t ldx, void* y, int64_t ldy, int64_t n_rows, int32_t d,
@@ -1400,10 +1452,9 @@ extern "C" int sgf_spmm_blocked(const int64_t* rowptr, const int32_t* ecode, con
   if (n_rows == 0 || d == 0) return SGF_OK;
   SGF_REQUIRE(rowptr && ecode && eval && nlds && sh_ptr && sh_cols && x && y, SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE(d <= 256, SGF_E_UNSUPPORTED, "%s: d = %d > 256 (one wave per row)", fn, d);
-  SGF_REQUIRE(rows_per_block >= kBlkRowsPerWave && rows_per_block <= 128 && rows_per_block % kBlkRowsPerWave == 0,
-              SGF_E_INVALID, "%s: rows_per_block must be a multiple of %d in [%d, 128]", fn, kBlkRowsPerWave,
+  SGF_REQUIRE(blk_rows_ok(rows_per_block), SGF_E_INVALID, "%s: rows_per_block must be a multiple of %d in [%d, 128]", fn, kBlkRowsPerWave,
               kBlkRowsPerWave);
-  SGF_REQUIRE(lds_rows >= 1 && lds_rows <= sgf_spmm_lds_rows_len(dtype), SGF_E_INVALID,
+  SGF_REQUIRE(blk_lds_rows_ok(lds_rows, dtype), SGF_E_INVALID,
               "%s: lds_rows %d outside [1, %d]", fn, lds_rows, sgf_spmm_lds_rows_len(dtype));
   if (const int rc = check_spmm_operands(fn, x, ldx, y, ldy, d, dtype)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
