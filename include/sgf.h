@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 662 /* 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 663 /* 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -186,6 +186,29 @@ int sgf_spmm_split(const int64_t* rowptr, const int32_t* colind, const float* va
                    int64_t ldx, int64_t n_cols, void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype,
                    int64_t long_len, int64_t long_segments, void* workspace, size_t workspace_bytes,
                    void* stream);
+
+/* sgf_spmm_split with a PACKED copy of x next to the dense one (bf16, d = 256; written by sgf_bn_apply_packed below).
+ * On a graph without locality the launch is bound by the bytes of its gathers, and an operand that is the output of a
+ * ReLU holds many exact zeros.  Packed row format: one slot of slot_bytes (384 or 448) per row of x, 128-byte aligned:
+ *     bytes [0, 32)  a 256-bit mask, bit c (byte c / 8, bit c % 8) set iff the bf16 bits of column c are not 0x0000
+ *                    (-0.0 is a value);
+ *     bytes [32, ..) the bf16 values of the set columns in column order, at most (slot_bytes - 32) / 2 = 176 / 208;
+ *     the rest zero.  A slot decodes to the dense row bit for bit.
+ * `packed` holds sgf_spmm_packed_bytes(n_cols, slot_bytes) bytes (the slots and a tail the kernel may read, never uses);
+ * `overflow` (device int32 [1]) is the producer's count of rows with more non-zeros than a slot holds.  The launch reads
+ * it ON THE DEVICE: zero -> it gathers the slots (slot_bytes / 512 of the dense bytes), anything else -> the dense rows,
+ * all or nothing.  It decodes the same four bf16 per lane and runs the same fp32 FMAs in the same order, so y equals
+ * sgf_spmm_split's bit for bit either way.  The slots are gathered only where sgf_spmm_packed_supported answers 1 — the
+ * launch would run the wave-per-row kernel (sgf_spmm_arm = 2) on bf16 rows of exactly 256 columns, SGF_SPMM_PACKED != 0
+ * (cached switch) — every other launch is sgf_spmm_split's on the dense rows; rows longer than long_len go to the long-row
+ * queue as in sgf_spmm_split and are reduced from the dense rows. */
+size_t sgf_spmm_packed_bytes(int64_t n, int32_t slot_bytes);
+int32_t sgf_spmm_packed_supported(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols, int32_t aligned16,
+                                  int32_t slot_bytes);
+int sgf_spmm_packed(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,
+                    int64_t n_cols, const void* packed, int32_t slot_bytes, const int32_t* overflow, void* y, int64_t ldy,
+                    int64_t n_rows, int32_t d, int32_t dtype, int64_t long_len, int64_t long_segments, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* sgf_spmm_split for a CSR whose gathers mostly hit in L2 (a locality-restoring node order, sgf_reorder
  * below).  The vector memory pipe's address rate is per LANE, so bf16 rows (512 B) are then fetched TWO per
@@ -678,6 +701,13 @@ int sgf_bn_apply(const void* x, int64_t ldx, const float* mean, const float* rst
                  const float* gamma, const float* beta, const void* res, int64_t ldr,
                  int32_t relu, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
                  void* stream);
+/* sgf_bn_apply that ALSO writes every row of y in the packed form sgf_spmm_packed gathers (format above; bf16, d = 256,
+ * rows 16-byte aligned, `packed` 128-byte aligned with sgf_spmm_packed_bytes(n, slot_bytes) bytes): y is sgf_bn_apply's bit
+ * for bit.  *overflow (device int32) = the number of rows with more non-zeros than a slot holds (an integer count: exact,
+ * order-independent); such a row's slot holds the values that fit and is never decoded. */
+int sgf_bn_apply_packed(const void* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                        const float* beta, const void* res, int64_t ldr, int32_t relu, int64_t n, int32_t d, int32_t dtype,
+                        void* y, int64_t ldy, void* packed, int32_t slot_bytes, int32_t* overflow, void* stream);
 int sgf_bn_bwd_stats(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* mean,
                      const float* rstd, const float* gamma, const float* beta, int32_t relu,
                      int64_t n, int32_t d, int32_t dtype, float* stats, void* workspace,

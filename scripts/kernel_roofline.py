@@ -110,6 +110,12 @@ def main(path: str, elem: int):
         ("k_ln_bwd_bf16x8", ("k_ln_bwd_bf16x8<",), 4 * T, "post-attention only (g, x, res in — no activation follows, so y is not read; one shared dx out: 4T, as the PMC pass measures); 16 B per lane (r06)", find),
         ("k_bn_apply_bf16x8<residual>", ("k_bn_apply_bf16x8<true",), 3 * T, "the three layers: z, residual -> x'; 16 B per lane (r06)", find),
         ("k_bn_apply_bf16x8<no residual>", ("k_bn_apply_bf16x8<false",), 2 * T, "the stem", find),
+        # the forward GCN SpMM of layer 1 on packed operand rows: its producer writes 384 of 512 bytes per row more
+        ("k_bn_apply_bf16x8_packed<no residual, 384>", ("k_bn_apply_bf16x8_packed<false", "384>"), 2.75 * T,
+         "the stem: z -> x0 and its 384-byte slots (0.75 T)", find),
+        ("k_spmm_row_packed<384>", ("k_spmm_row_packed<384",), csr + 1.75 * T,
+         "layer 1 forward, gather-bound: {:.1f} GB of 384-B slot fetches per launch".format(
+             (NNZ * (8 + 384) + (N + 1) * 8) / 1e9 + T), find),
         ("k_bn_bwd_stats_bf16x8<one gradient>", ("k_bn_bwd_stats_bf16x8<false",), 2 * T, "the three layers (g, z)", find),
         ("k_bn_bwd_stats_bf16x8<two gradients>", ("k_bn_bwd_stats_bf16x8<true",), 3 * T, "the stem (g1, g2, z)", find),
         ("k_bn_bwd_apply_bf16x8", ("k_bn_bwd_apply_bf16x8<",), 3 * T, "g, z -> dz", find),

@@ -48,6 +48,10 @@ SIGNATURES = {
     "sgf_spmm_split_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_spmm_split": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int64,
                                  c_int64, _P, c_size_t, _P]),
+    "sgf_spmm_packed_bytes": (c_size_t, [c_int64, c_int32]),
+    "sgf_spmm_packed_supported": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32]),
+    "sgf_spmm_packed": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int32, _P, _P, c_int64, c_int64, c_int32, c_int32,
+                                  c_int64, c_int64, _P, c_size_t, _P]),
     "sgf_spmm_stream": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int64,
                                   c_int64, _P, c_size_t, _P]),
     "sgf_reorder_workspace_bytes": (c_size_t, [c_int64, c_int64]),
@@ -142,6 +146,8 @@ SIGNATURES = {
     "sgf_bn_finalize": (c_int32, [_P, _P, c_double, c_float, c_float, _P, _P, c_int32, _P, _P, _P]),
     "sgf_bn_apply": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32,
                                c_int32, _P, c_int64, _P]),
+    "sgf_bn_apply_packed": (c_int32, [_P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, _P,
+                                      c_int64, _P, c_int32, _P, _P]),
     "sgf_bn_bwd_stats": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int32, c_int64, c_int32,
                                    c_int32, _P, _P, c_size_t, _P]),
     "sgf_bn_bwd_stats2": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int32, c_int64, c_int32,

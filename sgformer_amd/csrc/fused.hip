@@ -620,6 +620,104 @@ __global__ __launch_bounds__(kThreads) void k_bn_apply_bf16x8(const uint16_t* __
   }
 }
 
+// ---- the same pass, also writing every output row in PACKED form for the SpMM that gathers it next (spmm.hip:
+// k_spmm_row_packed).  d = 256: 32 lanes hold a row, 8 columns each.  Slot of S bytes per row = 32 bytes of non-zero mask
+// (bit c = column c, little-endian) + the non-zero bf16 values in column order, at most (S - 32) / 2 of them.  Non-zero =
+// bf16 bits != 0, so -0.0 is a value and a slot decodes to the dense row bit for bit.  A row is compacted in LDS (the lane's
+// first value goes to the exclusive prefix of the lanes' counts) and leaves as 16-byte stores; bytes behind the last value
+// are zero.  A row with more non-zeros than the slot holds writes the values that fit and is counted in *overflow
+// (integer atomicAdd, one per block: order-independent); the gather then reads the dense rows for the whole launch.
+typedef uint16_t __attribute__((may_alias)) ew_u16a;
+typedef uint4 __attribute__((may_alias)) ew_uint4a;
+
+template <bool kRes, int U, int S>
+__global__ __launch_bounds__(kThreads) void k_bn_apply_bf16x8_packed(const uint16_t* __restrict__ x, int64_t ldx, BnParams p,
+                                                                     const uint16_t* __restrict__ res, int64_t ldr, int relu,
+                                                                     int64_t n, uint16_t* __restrict__ y, int64_t ldy,
+                                                                     uint4* __restrict__ packed, int32_t* __restrict__ overflow) {
+  constexpr int kCap = (S - 32) / 2;      // values a slot holds
+  constexpr int kQ = S / 16;              // 16-byte pieces of a slot
+  constexpr int rpp = kThreads / 32;
+  __shared__ __align__(16) unsigned char stage[rpp][S];
+  const int q = threadIdx.x & 31;
+  const int sr = threadIdx.x >> 5;
+  const int col = q * 8;
+  BnCoeffs8 c;
+  bn_coeffs8(p, col, c);
+  unsigned char* const slot = stage[sr];
+  int over = 0;
+  const int64_t rpb = static_cast<int64_t>(rpp) * U;
+  for (int64_t row0 = static_cast<int64_t>(blockIdx.x) * rpb + sr; row0 < n; row0 += static_cast<int64_t>(gridDim.x) * rpb) {
+    uint4 xv[U], rv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = row0 + u * rpp;
+      if (row < n) {
+        xv[u] = *reinterpret_cast<const uint4*>(x + row * ldx + col);
+        if (kRes) rv[u] = *reinterpret_cast<const uint4*>(res + row * ldr + col);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t row = row0 + u * rpp;
+      const bool live = row < n;          // the same for the 32 lanes of a row
+      uint4 ov = make_uint4(0u, 0u, 0u, 0u);
+      if (live) {
+        float v[8], r[8], o[8];
+        ew_unpack(xv[u], v);
+        if (kRes) ew_unpack(rv[u], r);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          o[e] = fmaf((v[e] - c.mu[e]) * c.rs[e], c.ga[e], c.be[e]);   // (k_bn_apply_bf16x8's arithmetic, term by term)
+          if (relu) o[e] = fmaxf(o[e], 0.f);
+          if (kRes) o[e] += r[e];
+        }
+        ov = ew_pack8(o);
+        *reinterpret_cast<uint4*>(y + row * ldy + col) = ov;
+      }
+      const uint32_t w[4] = {ov.x, ov.y, ov.z, ov.w};
+      uint32_t m8 = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) != 0) m8 |= 1u << e;
+      const int cnt = __popc(m8);
+      int incl = cnt;                     // inclusive prefix over the row's 32 lanes
+#pragma unroll
+      for (int off = 1; off < 32; off <<= 1) {
+        const int t = __shfl_up(incl, off, 32);
+        if (q >= off) incl += t;
+      }
+      const int total = __shfl(incl, 31, 32);
+      if (live && q == 0 && total > kCap) ++over;
+      if (q < kQ) reinterpret_cast<ew_uint4a*>(slot)[q] = make_uint4(0u, 0u, 0u, 0u);
+      // (the slot is written and read back by different lanes of ONE wave: LDS executes a wave's instructions in order, the
+      // compiler must not re-order them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      slot[q] = static_cast<unsigned char>(m8);
+      int pos = incl - cnt;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (m8 & (1u << e)) {
+          if (pos < kCap) *reinterpret_cast<ew_u16a*>(slot + 32 + 2 * pos) = static_cast<uint16_t>(w[e >> 1] >> (16 * (e & 1)));
+          ++pos;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (live && q < kQ) packed[row * kQ + q] = reinterpret_cast<const ew_uint4a*>(slot)[q];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) over += __shfl_xor(over, off, 64);
+  if ((threadIdx.x & 63) == 0 && over > 0) atomicAdd(overflow, over);
+}
+
 template <int U>
 __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply_bf16x8(
     const uint16_t* __restrict__ dy, int64_t lddy, const uint16_t* __restrict__ x, int64_t ldx, BnParams p, int relu,
@@ -1544,6 +1642,41 @@ extern "C" int sgf_bn_apply(const void* x, int64_t ldx, const float* mean, const
     hipLaunchKernelGGL((k_bn_apply<uint16_t>), grid, dim3(kThreads), 0, st,
                        static_cast<const uint16_t*>(x), ldx, p, static_cast<const uint16_t*>(res),
                        ldr, relu, n, d, static_cast<uint16_t*>(y), ldy);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+extern "C" int sgf_bn_apply_packed(const void* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, const void* res, int64_t ldr, int32_t relu, int64_t n, int32_t d,
+                                   int32_t dtype, void* y, int64_t ldy, void* packed, int32_t slot_bytes, int32_t* overflow,
+                                   void* stream) {
+  const char* fn = "sgf_bn_apply_packed";
+  SGF_REQUIRE(x && y && mean && rstd && packed && overflow, SGF_E_INVALID, "%s: null pointer", fn);
+  int rc = check_ew(fn, n, d, dtype);
+  if (rc != SGF_OK) return rc;
+  SGF_REQUIRE(dtype == SGF_BF16 && d == 256, SGF_E_UNSUPPORTED, "%s: packed rows are bf16 rows of 256 columns", fn);
+  SGF_REQUIRE(slot_bytes == 384 || slot_bytes == 448, SGF_E_UNSUPPORTED, "%s: slot_bytes must be 384 or 448", fn);
+  SGF_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (!res || ldr % 8 == 0) && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(y) % 16 == 0 && (!res || reinterpret_cast<uintptr_t>(res) % 16 == 0) &&
+                  reinterpret_cast<uintptr_t>(packed) % 128 == 0,
+              SGF_E_INVALID, "%s: rows must be 16-byte aligned, the packed buffer 128-byte aligned", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  SGF_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), st));
+  if (n == 0) return SGF_OK;
+  const BnParams p{mean, rstd, gamma, beta};
+  const dim3 g8(rowwalk8_grid(n, d));
+#define SGF_BNP(RES_, S_)                                                                                                 \
+  hipLaunchKernelGGL((k_bn_apply_bf16x8_packed<RES_, kEw8Unroll, S_>), g8, dim3(kThreads), 0, st,                         \
+                     static_cast<const uint16_t*>(x), ldx, p, static_cast<const uint16_t*>(res), ldr, relu, n,            \
+                     static_cast<uint16_t*>(y), ldy, static_cast<uint4*>(packed), overflow)
+  if (res) {
+    if (slot_bytes == 384) SGF_BNP(true, 384);
+    else SGF_BNP(true, 448);
+  } else {
+    if (slot_bytes == 384) SGF_BNP(false, 384);
+    else SGF_BNP(false, 448);
+  }
+#undef SGF_BNP
   SGF_LAUNCH_CHECK();
   return SGF_OK;
 }

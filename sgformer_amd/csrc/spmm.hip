@@ -213,6 +213,219 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_spmm_row(
   if (active) store4<T>(y + row * ldy + fc, acc);
 }
 
+// ---- wave per row, gathering PACKED operand rows (bf16, d = 256) ---------------------------------------------
+// k_spmm_row on the uniform graph is bound by the bytes of its gathers (random 512-byte rows at the fabric's rate,
+// profiles/r02_gather_probe.md), and the operand of the first GCN layer is relu(BatchNorm(.)): half of it is exact zeros.
+// Its producer (fused.hip: k_bn_apply_bf16x8_packed) also writes every row as a slot of S bytes — 32 bytes of non-zero mask
+// (bit c = column c), then the non-zero bf16 values in column order — and this kernel gathers the slots: S / 512 of the bytes.
+// Same row map, XCD remap, scalar CSR loads, long-row hand-off and batch structure as k_spmm_row; per stored entry
+//   1. lane l loads mask word l / 8 (its 4 columns are bits 4 (l % 8) .. + 3 of that word);
+//   2. its first value sits behind `pre` = the set bits below column 4 l: the words before (popcounts summed across the 8
+//      lane groups by three DPP steps) + the bits below its own nibble; it loads 12 bytes from the 4-byte boundary under it;
+//   3. an alignbit pair shifts the odd case down, and one v_perm per column places the column's value (or zero bytes, for a
+//      clear mask bit) in the high half of an fp32 — selectors by nibble from a 16-entry LDS table.
+// Decoding rebuilds the four bf16 of the dense row bit for bit — zeros included: all four FMAs of an entry are issued, none
+// is skipped — and the FMAs are k_spmm_row's in k_spmm_row's order, so the result is identical.  The producer counts the rows that did not fit their slot in *overflow: the wave reads it first
+// (uniform, scalar) and, if it is not zero, gathers the dense rows instead — the whole launch, no host read.
+// The values of the last slot are read up to 12 bytes past it: the buffer carries kPackedTail bytes of padding.
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+constexpr int kPackedMaskBytes = 32;
+constexpr int kPackedTail = 128;
+
+struct DenseRowLoader {
+  static constexpr bool kAhead = false;
+  __amdgpu_buffer_rsrc_t rsrc;
+  int voff;
+  uint32_t pitch;
+  template <int N> struct Batch { u32x2 raw[N]; };
+  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N]) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) b.raw[u] = BufRow<uint16_t>::load(rsrc, voff, static_cast<uint32_t>(c[u]) * pitch);
+  }
+  template <int N> __device__ __forceinline__ void follow(Batch<N>&) const {}
+  template <int N> __device__ __forceinline__ void apply(const Batch<N>& b, const float (&v)[N], float4& acc) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) fma4(acc, v[u], BufRow<uint16_t>::widen(b.raw[u]));
+  }
+};
+
+template <int S>
+struct PackedRowLoader {
+  static constexpr bool kAhead = true;
+  __amdgpu_buffer_rsrc_t rsrc;
+  int mask_voff;        // byte offset of this lane's mask word in a slot
+  int shift;            // bit position of this lane's nibble in that word
+  uint32_t below;       // the bits of the word under the nibble
+  const uint4* lut;     // LDS: nibble -> the four v_perm selectors
+  template <int N> struct Batch {
+    uint32_t slot[N], mw[N], pre[N];
+    u32x3 raw[N];
+  };
+  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N]) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      b.slot[u] = static_cast<uint32_t>(c[u]) * static_cast<uint32_t>(S);
+      b.mw[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, mask_voff, static_cast<int>(b.slot[u]), 0);
+    }
+  }
+  template <int N> __device__ __forceinline__ void follow(Batch<N>& b) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const int t = __popc(b.mw[u]);
+      // inclusive sum of the words' popcounts over the 8 lane groups (a DPP row = two groups)
+      int s = t + __builtin_amdgcn_update_dpp(0, t, 0x118, 0xf, 0xf, true);     // row_shr:8
+      s += __builtin_amdgcn_update_dpp(0, s, 0x142, 0xa, 0xf, false);           // row_bcast:15 -> rows 1, 3
+      s += __builtin_amdgcn_update_dpp(0, s, 0x143, 0xc, 0xf, false);           // row_bcast:31 -> rows 2, 3
+      b.pre[u] = static_cast<uint32_t>(s - t) + __popc(b.mw[u] & below);
+      const uint32_t off = ((b.pre[u] & ~1u) << 1) + (b.slot[u] + kPackedMaskBytes);
+      b.raw[u] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, static_cast<int>(off), 0, 0);
+    }
+  }
+  template <int N> __device__ __forceinline__ void apply(const Batch<N>& b, const float (&v)[N], float4& acc) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const uint4 sel = lut[(b.mw[u] >> shift) & 15u];
+      const uint32_t sh = b.pre[u] << 4;                                        // alignbit reads 5 bits: 0 or 16
+      const uint32_t lo = __builtin_amdgcn_alignbit(b.raw[u].y, b.raw[u].x, sh);
+      const uint32_t hi = __builtin_amdgcn_alignbit(b.raw[u].z, b.raw[u].y, sh);
+      float4 f;
+      f.x = __uint_as_float(__builtin_amdgcn_perm(hi, lo, sel.x));
+      f.y = __uint_as_float(__builtin_amdgcn_perm(hi, lo, sel.y));
+      f.z = __uint_as_float(__builtin_amdgcn_perm(hi, lo, sel.z));
+      f.w = __uint_as_float(__builtin_amdgcn_perm(hi, lo, sel.w));
+      fma4(acc, v[u], f);
+    }
+  }
+};
+
+template <int N, typename L>
+__device__ __forceinline__ void gather_batch_with(const L& ld, const int32_t* __restrict__ colind,
+                                                  const float* __restrict__ val, int e, float4& acc) {
+  int32_t c[N];
+  float v[N];
+  typename L::template Batch<N> b;
+#pragma unroll
+  for (int u = 0; u < N; ++u) {
+    c[u] = colind[e + u];
+    v[u] = val[e + u];
+  }
+  ld.request(b, c);
+  ld.follow(b);
+  ld.apply(b, v, acc);
+}
+
+// one row of k_spmm_row — the same batches, tail ladder and FMA order — with the rows fetched by `ld`.  k_spmm_row itself is
+// NOT re-expressed through this walker: it runs five of the six SpMM launches of a step and its code is left as measured
+// (a dense step must not move with this arm); the two copies are bound by tests/test_gpu_spmm_packed.py, which compares
+// this walker's dense form (overflow count raised) and its packed form with k_spmm_row bit for bit on a row-length ladder.  A loader with
+// kAhead requests the NEXT batch (its mask words) before the current batch's FMAs: the packed gather is two dependent
+// memory round trips per batch (masks, then values), and with one batch per wave in flight the launch has too few bytes
+// outstanding to keep the fabric busy: back to back on the products-size uniform graph 9.1 ms without, 8.4-8.6 ms with the
+// masks a batch ahead, the dense kernel 10.2-10.3 ms; inside the traced training step 8.86 ms against 9.9-10.0 ms
+// (profiles/spmm_packed_kernel_stats.md).  74 VGPRs, 6 waves per SIMD (24 per CU) against k_spmm_row's 40 and 8: the second
+// batch's mask words and prefixes are live across the first batch's FMAs.
+template <int UNROLL, typename L>
+__device__ __forceinline__ float4 walk_row(const L& ld, const int32_t* __restrict__ ci, const float* __restrict__ va, int len) {
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  int i = 0;
+  if (UNROLL <= len) {
+    int32_t c0[UNROLL], c1[UNROLL];
+    float v0[UNROLL], v1[UNROLL];
+    typename L::template Batch<UNROLL> ba, bb;
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      c0[u] = ci[u];
+      v0[u] = va[u];
+    }
+    ld.request(ba, c0);
+    for (;;) {
+      i += UNROLL;
+      const bool more_a = i + UNROLL <= len;
+      if (more_a) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+          c1[u] = ci[i + u];
+          v1[u] = va[i + u];
+        }
+      }
+      ld.follow(ba);
+      if (L::kAhead && more_a) ld.request(bb, c1);
+      ld.apply(ba, v0, acc);
+      if (!more_a) break;
+      if (!L::kAhead) ld.request(bb, c1);
+      i += UNROLL;
+      const bool more_b = i + UNROLL <= len;
+      if (more_b) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+          c0[u] = ci[i + u];
+          v0[u] = va[i + u];
+        }
+      }
+      ld.follow(bb);
+      if (L::kAhead && more_b) ld.request(ba, c0);
+      ld.apply(bb, v1, acc);
+      if (!more_b) break;
+      if (!L::kAhead) ld.request(ba, c0);
+    }
+  }
+  if (i + 4 <= len) { gather_batch_with<4>(ld, ci, va, i, acc); i += 4; }
+  if (i + 2 <= len) { gather_batch_with<2>(ld, ci, va, i, acc); i += 2; }
+  if (i < len) gather_batch_with<1>(ld, ci, va, i, acc);
+  return acc;
+}
+
+template <int S, int UNROLL>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void k_spmm_row_packed(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colind, const float* __restrict__ val,
+    const uint16_t* __restrict__ x, uint32_t pitch, uint32_t x_bytes, const void* __restrict__ packed, uint32_t packed_bytes,
+    const int32_t* __restrict__ overflow, uint16_t* __restrict__ y, int64_t ldy, int64_t n_rows, LongQueue lq) {
+  __shared__ uint4 lut[16];
+  if (threadIdx.x < 16) {
+    // column k of a lane whose nibble is threadIdx.x: bytes {0, 0, value lo, value hi} with the value at index
+    // popc(nibble below k) of the lane's 8 bytes, or four zero bytes (selector 0x0c) when bit k is clear
+    uint32_t s[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t i = __popc(threadIdx.x & ((1u << k) - 1u));
+      s[k] = (threadIdx.x >> k) & 1u ? ((2u * i + 1u) << 24) | ((2u * i) << 16) | 0x0c0cu : 0x0c0c0c0cu;
+    }
+    lut[threadIdx.x] = make_uint4(s[0], s[1], s[2], s[3]);
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t row = blk * kWavesPerBlock + wid;  // wave-uniform
+  if (row >= n_rows) return;
+  const int64_t e0 = rowptr[row];
+  const int64_t e1 = rowptr[row + 1];
+  if (e1 - e0 > lq.long_len) {   // wave-uniform
+    push_long_row(lq, row, e1 - e0, lane, 64);
+    return;
+  }
+  const int32_t* __restrict__ ci = colind + e0;
+  const float* __restrict__ va = val + e0;
+  const int len = static_cast<int>(e1 - e0);
+  float4 acc;
+  if (*overflow == 0) {          // wave-uniform: a scalar load
+    PackedRowLoader<S> ld;
+    ld.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(packed), 0, packed_bytes, 0x00020000);
+    ld.mask_voff = (lane >> 3) * 4;
+    ld.shift = (lane & 7) * 4;
+    ld.below = (1u << ld.shift) - 1u;
+    ld.lut = lut;
+    acc = walk_row<UNROLL>(ld, ci, va, len);
+  } else {
+    DenseRowLoader ld;
+    ld.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), 0, x_bytes, 0x00020000);
+    ld.voff = lane * 8;
+    ld.pitch = pitch;
+    acc = walk_row<UNROLL>(ld, ci, va, len);
+  }
+  store4<uint16_t>(y + row * ldy + lane * 4, acc);
+}
+
 // ---- flattened (segmented) wave kernel --------------------------------------------------------------------
 // Why: with ~46 stored entries per row, a wave-per-row kernel spends its life in a chain of DEPENDENT memory
 // latencies — kernel arguments, rowptr, then per 8-entry batch (codes/values -> gathers), then a tail ladder —
@@ -1242,10 +1455,26 @@ Choice choose_for_operands(int32_t d, size_t elem_size, int64_t ldx, int64_t ldy
   return choose_kernel(d, elem_size, fits32, pair_ok, stream, g_forced.get());
 }
 
+// The packed copy of the operand of one launch (sgf_spmm_packed): slots of `slot_bytes` per source row and the device
+// count of rows that did not fit theirs.  The one rule for when the launch gathers it — shared by launch and
+// sgf_spmm_packed_supported: SGF_SPMM_PACKED != 0, bf16 rows of exactly 256 columns, the launch would run k_spmm_row,
+// 384- or 448-byte slots within 32-bit offsets.  (Rows handed to the long-row queue are reduced from the dense rows.)
+EnvInt g_packed{"SGF_SPMM_PACKED", 1};
+struct PackedOperand {
+  const void* slots;
+  int32_t slot_bytes;
+  const int32_t* overflow;
+};
+bool packed_rule(const Choice& c, int32_t d, size_t elem_size, int64_t n_cols, int32_t slot_bytes) {
+  return g_packed.get() != 0 && c.arm == Arm::Row && elem_size == 2 && d == 256 &&
+         (slot_bytes == 384 || slot_bytes == 448) &&
+         static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(slot_bytes) + kPackedTail < (static_cast<uint64_t>(1) << 32);
+}
+
 template <typename T>
 int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const T* x, int64_t ldx, int64_t n_cols,
            T* y, int64_t ldy, int64_t n_rows, int32_t d, hipStream_t st, const LongQueue& lq,
-           float* partial, bool stream) {
+           float* partial, bool stream, const PackedOperand* pk = nullptr) {
   constexpr int UNROLL = 8;
   const dim3 block(kWavesPerBlock * 64);
   uint64_t x_bytes;
@@ -1275,6 +1504,18 @@ int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const
                          static_cast<uint32_t>(x_bytes), y, ldy, n_rows, d, chunk, lq);
       break;
     case Arm::Row:
+      if (pk && packed_rule(c, d, sizeof(T), n_cols, pk->slot_bytes)) {
+        const uint32_t pk_bytes = static_cast<uint32_t>(n_cols * pk->slot_bytes + 16);   // (values are read 12 bytes past a slot)
+#define SGF_ROWP(S_)                                                                                                  \
+  hipLaunchKernelGGL((k_spmm_row_packed<S_, UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st, rowptr, colind, \
+                     val, reinterpret_cast<const uint16_t*>(x), static_cast<uint32_t>(ldx * sizeof(T)),               \
+                     static_cast<uint32_t>(x_bytes), pk->slots, pk_bytes, pk->overflow, reinterpret_cast<uint16_t*>(y), \
+                     ldy, n_rows, lq)
+        if (pk->slot_bytes == 384) SGF_ROWP(384);
+        else SGF_ROWP(448);
+#undef SGF_ROWP
+        break;
+      }
       hipLaunchKernelGGL((k_spmm_row<T, UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st, rowptr, colind,
                          val, x, static_cast<uint32_t>(ldx * sizeof(T)), static_cast<uint32_t>(x_bytes), y, ldy,
                          n_rows, d, lq);
@@ -1343,7 +1584,7 @@ int check_spmm_operands(const char* fn, const void* x, int64_t ldx, const void* 
 
 int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,
                 int64_t n_cols, void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, const LongQueue& lq,
-                float* partial, hipStream_t st, const char* fn, bool stream = false) {
+                float* partial, hipStream_t st, const char* fn, bool stream = false, const PackedOperand* pk = nullptr) {
   SGF_REQUIRE(n_rows >= 0 && d >= 0 && n_cols >= 0, SGF_E_INVALID, "%s: negative size", fn);
   if (n_rows == 0 || d == 0) return SGF_OK;
   SGF_REQUIRE(rowptr && x && y, SGF_E_INVALID, "%s: null pointer", fn);
@@ -1354,7 +1595,7 @@ int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, 
     return launch<float>(rowptr, colind, val, static_cast<const float*>(x), ldx, n_cols, static_cast<float*>(y), ldy,
                          n_rows, d, st, lq, partial, stream);
   return launch<uint16_t>(rowptr, colind, val, static_cast<const uint16_t*>(x), ldx, n_cols,
-                          static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream);
+                          static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream, pk);
 }
 }  // namespace
 
@@ -1416,6 +1657,39 @@ extern "C" int sgf_spmm_split(const int64_t* rowptr, const int32_t* colind, cons
                               size_t workspace_bytes, void* stream) {
   return spmm_split_impl(false, "sgf_spmm_split", rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype,
                          long_len, long_segments, workspace, workspace_bytes, stream);
+}
+
+// sgf_spmm_split with a packed copy of x next to it (fused.hip: sgf_bn_apply_packed).  The launch gathers the slots when
+// packed_rule holds and the producer counted no overflowing row (read on the device); anything else runs sgf_spmm_split's
+// kernels on the dense rows, and so do the rows longer than long_len in every case.  Results are those of sgf_spmm_split
+// bit for bit either way.
+extern "C" size_t sgf_spmm_packed_bytes(int64_t n, int32_t slot_bytes) {
+  if (n < 0 || slot_bytes <= 0) return 0;
+  return static_cast<size_t>(n) * static_cast<size_t>(slot_bytes) + kPackedTail;
+}
+
+extern "C" int32_t sgf_spmm_packed_supported(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols,
+                                             int32_t aligned16, int32_t slot_bytes) {
+  if (dtype != SGF_F32 && dtype != SGF_BF16) return 0;
+  const size_t esz = dtype == SGF_BF16 ? 2 : 4;
+  const Choice c = choose_for_operands(d, esz, ldx, ldy, n_cols, aligned16 != 0, false);
+  return packed_rule(c, d, esz, n_cols, slot_bytes) ? 1 : 0;
+}
+
+extern "C" int sgf_spmm_packed(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,
+                               int64_t n_cols, const void* packed, int32_t slot_bytes, const int32_t* overflow, void* y,
+                               int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, int64_t long_len, int64_t long_segments,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "sgf_spmm_packed";
+  SGF_REQUIRE(packed && overflow, SGF_E_INVALID, "%s: null pointer", fn);
+  SGF_REQUIRE(slot_bytes == 384 || slot_bytes == 448, SGF_E_UNSUPPORTED, "%s: slot_bytes must be 384 or 448", fn);
+  SGF_REQUIRE(reinterpret_cast<uintptr_t>(packed) % 128 == 0, SGF_E_INVALID, "%s: the packed buffer must be 128-byte aligned", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LongQueue lq;
+  float* partial;
+  if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
+  const PackedOperand pk{packed, slot_bytes, overflow};
+  return spmm_common(rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype, lq, partial, st, fn, false, &pk);
 }
 
 // sgf_spmm_split for a CSR whose gathers mostly hit in L2 (a locality-restoring node order, sgf_reorder): bf16 rows

@@ -479,26 +479,41 @@ def _own_block_spmm(graph, plan, own, x, n_local: int, transposed: bool):
 
 class _SpMM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, graph, shard):
+    def forward(ctx, x, graph, shard, packed=None):
         K.check(x)
         ctx.graph, ctx.shard = graph, shard
         if shard is not None:
             # node-sharded: rows of A local, X rows gathered from all ranks (halo all-gather)
             return _sharded_spmm(graph, x, shard, False)
-        return spmm_on(graph, x, False)
+        return spmm_on(graph, x, False, packed=packed)
 
     @staticmethod
     def backward(ctx, gy):
         graph, shard = ctx.graph, ctx.shard
         if shard is not None:
             # dX_local = (A^T dY)[local rows]: local rows of the CSR of A^T times the sharded dY
-            return _sharded_spmm(graph, gy.contiguous(), shard, True), None, None
-        return spmm_on(graph, gy.contiguous(), True), None, None
+            return _sharded_spmm(graph, gy.contiguous(), shard, True), None, None, None
+        return spmm_on(graph, gy.contiguous(), True), None, None, None
 
 
-def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None) -> torch.Tensor:
+def _row_kernel_graph(graph) -> bool:
+    """spmm_on's last branch: no row-block plan, no tile plan, no locality hint — the launch that may run k_spmm_row."""
+    return not (getattr(graph, "blocked", False) or getattr(graph, "tiled", False) or getattr(graph, "locality", False))
+
+
+def spmm_packed_slot(graph, x_shape, dtype, slot_bytes: int) -> int:
+    """`slot_bytes` if A x for a contiguous x of this shape would gather a packed copy of x with slots of that size
+    (K.bn_apply_packed -> spmm(..., packed=...)), else 0: the graph takes the wave-per-row launch and the launcher's own
+    rule holds (bf16 rows of 256 columns, SGF_SPMM_PACKED).  Rows on the long-row path are reduced from the dense x."""
+    if not slot_bytes or not hasattr(K, "spmm_packed_supported") or not _row_kernel_graph(graph):
+        return 0
+    return slot_bytes if K.spmm_packed_supported(x_shape, dtype, slot_bytes) else 0
+
+
+def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None) -> torch.Tensor:
     """A x or A^T x on one GPU: the LDS-staged row-block kernel when the graph carries a plan for this
-    storage dtype (GraphView adopted a re-ordered CSR), else the wave-per-row kernel."""
+    storage dtype (GraphView adopted a re-ordered CSR), else the wave-per-row kernel.  `packed`: the producer's packed
+    copy of x (K.bn_apply_packed), gathered instead of x by the wave-per-row launch of A x."""
     rp, ci, va = graph.transposed() if transposed else (graph.rowptr, graph.colind, graph.val)
     segs = graph.t_long_segments if transposed else graph.long_segments
     plan = graph.plan(x.dtype, transposed) if (getattr(graph, "blocked", False) and x.shape[1] <= 256) else None
@@ -515,9 +530,14 @@ def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None) -> torch.Tensor:
             graph._tile_plans.clear()
     if getattr(graph, "locality", False):
         return K.spmm(rp, ci, va, x, graph.n, out=out, long_segments=segs, stream_hint=True)
+    if packed is not None and not transposed and out is None:
+        return K.spmm_packed(rp, ci, va, x, packed, graph.n, long_segments=segs)
     return K.spmm(rp, ci, va, x, graph.n, out=out, long_segments=segs)
 
 
-def spmm(graph, x: torch.Tensor, shard=None) -> torch.Tensor:
-    """Y = A X with A the cached normalised adjacency (torch_sparse.matmul(adj, x) in the reference)."""
-    return _SpMM.apply(x, graph, shard)
+def spmm(graph, x: torch.Tensor, shard=None, packed=None) -> torch.Tensor:
+    """Y = A X with A the cached normalised adjacency (torch_sparse.matmul(adj, x) in the reference).  `packed`: a packed
+    copy of X for the forward gathers (spmm_packed_slot says when one is of use); the backward never reads it."""
+    if packed is None:
+        return _SpMM.apply(x, graph, shard)
+    return _SpMM.apply(x, graph, shard, packed)

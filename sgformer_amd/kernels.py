@@ -18,6 +18,18 @@ _BF16 = torch.bfloat16
 LONG_ROW = 1024
 _SEGMENT = 1024   # = sgf_spmm_segment_len()
 
+# launches by entry, for the tests that have to see which path a step took
+counters = {"spmm_packed": 0}
+
+
+class PackedRows:
+    """The packed copy of a bf16 [n, 256] operand (include/sgf.h, sgf_spmm_packed): `slots` uint8, slot_bytes per row plus
+    the tail the gather may read; `overflow` device int32 [1], the rows that did not fit their slot."""
+    __slots__ = ("slots", "slot_bytes", "n", "overflow")
+
+    def __init__(self, slots, slot_bytes, n, overflow):
+        self.slots, self.slot_bytes, self.n, self.overflow = slots, slot_bytes, n, overflow
+
 
 # ------------------------------------------------------------------------------------------------
 # plumbing
@@ -355,6 +367,36 @@ class HipKernels:
             else:
                 _lib.call("sgf_spmm", _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(x), x.stride(0), x.shape[0],
                           _ptr(y), y.stride(0), n_rows, d, _code(x), _stream(x.device))
+        return y
+
+    # ---- T2 gathering zero-elided operand rows (bf16, d = 256; csrc/spmm.hip: k_spmm_row_packed) ----
+    @staticmethod
+    def spmm_packed_supported(x_shape, dtype, slot_bytes: int) -> bool:
+        """Would sgf_spmm_packed gather the slots for a contiguous operand of this shape (else it runs sgf_spmm_split's
+        kernels on the dense rows)?  The launcher's own rule, SGF_SPMM_PACKED included."""
+        n, d = int(x_shape[0]), int(x_shape[1])
+        if dtype != torch.bfloat16 or n == 0:
+            return False
+        return bool(_lib.load().sgf_spmm_packed_supported(d, _lib.SGF_BF16, d, d, n, 1, int(slot_bytes)))
+
+    @staticmethod
+    def spmm_packed(rowptr, colind, val, x: torch.Tensor, packed: "PackedRows", n_rows: int, long_segments: int = 0) -> torch.Tensor:
+        """K.spmm(rowptr, colind, val, x, n_rows, long_segments=...) bit for bit, gathering `packed` (bn_apply_packed's copy of
+        x) instead of x wherever the launch allows and no row overflowed its slot (decided on the device)."""
+        x = _rows(x)
+        d = x.shape[1]
+        if packed.n != x.shape[0]:
+            raise ValueError("spmm_packed: the packed copy has another number of rows than x")
+        y = torch.empty((n_rows, d), dtype=x.dtype, device=x.device)
+        if n_rows == 0 or d == 0:
+            return y
+        with torch.cuda.device(x.device):
+            ws = (_workspace(x.device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(long_segments, d))
+                  if long_segments > 0 else None)
+            _lib.call("sgf_spmm_packed", _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(x), x.stride(0), x.shape[0],
+                      _ptr(packed.slots), packed.slot_bytes, _ptr(packed.overflow), _ptr(y), y.stride(0), n_rows, d, _code(x),
+                      LONG_ROW, long_segments, _ptr(ws), 0 if ws is None else ws.numel(), _stream(x.device))
+        counters["spmm_packed"] += 1
         return y
 
     # ---- T2 with on-chip reuse: node order, row-block plan, LDS-staged SpMM ----
@@ -810,6 +852,21 @@ class HipKernels:
                       _ptr(res), _ld(res), int(relu), n, d, _code(x), _ptr(y), y.stride(0),
                       _stream(dev))
         return y
+
+    @staticmethod
+    def bn_apply_packed(x, mean, rstd, gamma, beta, res, relu: bool, slot_bytes: int):
+        """(bn_apply's y, its rows in packed form for spmm_packed).  bf16 rows of 256 columns."""
+        n, d = x.shape
+        dev = x.device
+        y = torch.empty((n, d), dtype=x.dtype, device=dev)
+        nbytes = _lib.load().sgf_spmm_packed_bytes(n, int(slot_bytes))
+        packed = PackedRows(torch.empty(nbytes, dtype=torch.uint8, device=dev), int(slot_bytes), n,
+                            torch.empty(1, dtype=torch.int32, device=dev))
+        with torch.cuda.device(dev):
+            _lib.call("sgf_bn_apply_packed", _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
+                      _ptr(res), _ld(res), int(relu), n, d, _code(x), _ptr(y), y.stride(0), _ptr(packed.slots),
+                      packed.slot_bytes, _ptr(packed.overflow), _stream(dev))
+        return y, packed
 
     @staticmethod
     def bn_bwd_stats(gy, x, mean, rstd, gamma, beta, relu: bool) -> torch.Tensor:

@@ -211,9 +211,11 @@ class _StemPairBN(torch.autograd.Function):
     (sgf_gram_bn_bwd): x is data, nobody else needs dz."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, ln_gamma=None, ln_beta=None, ln_cfg=None):
+    def forward(ctx, x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, ln_gamma=None, ln_beta=None, ln_cfg=None, pack=None):
         """ln_cfg = (eps, relu, affine) — not None: the third output is [relu](LayerNorm(y1)) (TransConv's stem, large/ours.py:
-        198-201) instead of y1, and its backward takes dW1 / db1 / d ln_gamma / d ln_beta from sgf_gram_ln_bwd."""
+        198-201) instead of y1, and its backward takes dW1 / db1 / d ln_gamma / d ln_beta from sgf_gram_ln_bwd.
+        pack = {"slot_bytes": S} — not None: the BatchNorm pass also writes x0 in packed form for the SpMM that gathers it
+        (K.bn_apply_packed), left in pack["out"]."""
         K.check(x)
         dt = x.dtype
         w0c, w1c = w0.to(dt), w1.to(dt)
@@ -248,7 +250,10 @@ class _StemPairBN(torch.autograd.Function):
         be32 = beta.detach().float().contiguous() if beta is not None else None
         mean = mean.detach().float().contiguous()
         rstd = rstd.detach().float().contiguous()
-        x0 = K.bn_apply(y0, mean, rstd, g32, be32, None, True)
+        if pack is not None:
+            x0, pack["out"] = K.bn_apply_packed(y0, mean, rstd, g32, be32, None, True, pack["slot_bytes"])
+        else:
+            x0 = K.bn_apply(y0, mean, rstd, g32, be32, None, True)
         out1, ln_saved = y1, (None, None, None, None, None)
         if ln_cfg is not None:
             eps, ln_relu, affine = ln_cfg
@@ -308,7 +313,7 @@ class _StemPairBN(torch.autograd.Function):
                                               "SGF_STEM_LN_FUSED=0")
             dx = K.gemm(dz, w0c)
             K.gemm(gl.contiguous(), w1c, out=dx, beta=1.0, addend=dx)
-        return dx, dw0, db0, dw1, db1, dgamma, dbeta, None, None, dlg, dlb, None
+        return dx, dw0, db0, dw1, db1, dgamma, dbeta, None, None, dlg, dlb, None, None
 
 
 def stem_pair_bn_supported(x, w0, w1) -> bool:
@@ -316,13 +321,13 @@ def stem_pair_bn_supported(x, w0, w1) -> bool:
             and K.gram_bn_bwd_supported(w0.shape[0], x.shape[1], x.dtype))
 
 
-def stem_pair_bn(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard=None, ln=None):
+def stem_pair_bn(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard=None, ln=None, pack=None):
     """(x0 for the layers, x0 for the first SpMM, y1): see _StemPairBN.  ln = (LayerNorm weight, bias, eps, relu): the third
-    output is [relu](LayerNorm(y1)) — TransConv's stem — when the shapes allow (stem_ln_supported)."""
+    output is [relu](LayerNorm(y1)) — TransConv's stem — when the shapes allow (stem_ln_supported).  pack: see _StemPairBN."""
     if ln is None:
-        return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard)
+        return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, None, None, None, pack)
     lg, lb, eps, relu = ln
-    return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, lg, lb, (eps, relu, lg is not None))
+    return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, lg, lb, (eps, relu, lg is not None), pack)
 
 
 def stem_ln_supported(x, w1) -> bool:
@@ -435,7 +440,8 @@ class _LinearBNActRes(torch.autograd.Function):
     (sgf_gcn_bn_bwd_dx), then the weight / bias gradients on sgf_gram."""
 
     @staticmethod
-    def forward(ctx, y, x0, w, b, gamma, beta, bn_hook, relu: bool, use_res: bool, shard, chain, first: bool):
+    def forward(ctx, y, x0, w, b, gamma, beta, bn_hook, relu: bool, use_res: bool, shard, chain, first: bool, pack=None):
+        # pack = {"slot_bytes": S}: the BatchNorm pass also writes `out` in packed form for the next SpMM (pack["out"])
         K.check(y, x0)
         dt = x0.dtype
         wc = w.detach().to(dt).contiguous()
@@ -453,7 +459,10 @@ class _LinearBNActRes(torch.autograd.Function):
         be32 = beta.detach().float().contiguous() if beta is not None else None
         mean = mean.detach().float().contiguous()
         rstd = rstd.detach().float().contiguous()
-        out = K.bn_apply(z, mean, rstd, g32, be32, xr if use_res else None, relu)
+        if pack is not None:
+            out, pack["out"] = K.bn_apply_packed(z, mean, rstd, g32, be32, xr if use_res else None, relu, pack["slot_bytes"])
+        else:
+            out = K.bn_apply(z, mean, rstd, g32, be32, xr if use_res else None, relu)
         ctx.save_for_backward(yr, xr, z, wc, g32, be32, mean, rstd)
         ctx.meta = (bool(relu), bool(use_res), bool(training), float(n_tot), shard, chain, bool(first), w.dtype,
                     None if b is None else b.dtype, None if gamma is None else gamma.dtype)
@@ -514,11 +523,11 @@ class _LinearBNActRes(torch.autograd.Function):
         dbeta = stats[:d].to(gdt) if be32 is not None else None
         if shard is not None and g32 is not None:
             dgamma, dbeta = shard.unsum(dgamma), shard.unsum(dbeta)
-        return dy, dx0, dw, db, dgamma, dbeta, None, None, None, None, None, None
+        return dy, dx0, dw, db, dgamma, dbeta, None, None, None, None, None, None, None
 
 
-def linear_bn_act_res(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first):
-    return _LinearBNActRes.apply(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first)
+def linear_bn_act_res(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first, pack=None):
+    return _LinearBNActRes.apply(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first, pack)
 
 
 def linear(x, w, b):

@@ -55,6 +55,14 @@ DEFAULT_COMPUTE_DTYPE = None
 import os as _os
 OVERLAP_BRANCHES = _os.environ.get("SGF_OVERLAP", "1") == "1"
 OVERLAP_MIN_NODES = 65536
+
+# GraphConv's forward SpMMs gather a zero-elided, packed copy of their operand where that moves fewer bytes (csrc/spmm.hip:
+# k_spmm_row_packed; SGF_SPMM_PACKED=0 turns it off): slot bytes per layer, 0 = the layer gathers the dense rows.  Layer 1
+# reads x0 = relu(BatchNorm(stem)): 119-128 non-zeros of 256 per row (sd 8, maximum 160) on the products recipe, so the
+# 176 values of a 384-byte slot lie 6 sd above the mean.  Layers 2 and 3 read relu(BatchNorm(z)) + x0: 190-195 non-zeros
+# (sd 7, maximum 227) against the 208 of a 448-byte slot, 2 sd, and 0.1-3 % of the rows overflow — one such row sends the
+# whole launch to the dense rows, so they stay dense (profiles/spmm_packed_zero_fractions.md).
+PACKED_SLOT_BYTES = (384, 0, 0)
 _side_streams = {}
 
 
@@ -163,8 +171,9 @@ class GraphConvLayer(nn.Module):
     def reset_parameters(self):
         self.W.reset_parameters()
 
-    def propagate(self, x, edge_index):
-        """A_norm x (large/ours.py:26-34): the cached CSR of `edge_index` times x."""
+    def propagate(self, x, edge_index, packed=None):
+        """A_norm x (large/ours.py:26-34): the cached CSR of `edge_index` times x.  `packed` (not in the reference
+        signature): the packed copy of x its producer wrote (GraphConv.pack_request), gathered instead of x."""
         shard = self._shard
         if isinstance(edge_index, ops.CSRGraph):   # SGFormer.forward resolved (and maybe re-ordered) it already
             graph = edge_index
@@ -174,7 +183,8 @@ class GraphConvLayer(nn.Module):
             # one GPU — or the batch mode of a sharded run (ShardContext.for_batch): this rank's own induced
             # subgraph, no halo; only the attention / BatchNorm partial sums cross ranks
             graph = ops.graph_cache.get(edge_index, x.shape[0])
-        return ops.spmm(graph, x, None if (shard is not None and shard.local_graph) else shard)
+        shard = None if (shard is not None and shard.local_graph) else shard
+        return ops.spmm(graph, x, shard, packed if shard is None else None)
 
     def forward(self, x, edge_index, x0, bn_stats=False):
         """`bn_stats` (not in the reference signature): also return the batch statistics (mean, var, count) of
@@ -288,6 +298,27 @@ class GraphConv(nn.Module):
             return mean, torch.rsqrt(var + bn.eps), n_tot, use_batch
         return hook
 
+    def pack_request(self, layer: int, n: int, dtype, edge_index):
+        """{"slot_bytes": S} if the SpMM of layer `layer` (0-based) should gather a packed copy of its operand — handed to
+        the BatchNorm node that produces the operand (ops.stem_pair_bn / ops.linear_bn_act_res), which leaves the copy in
+        ["out"] — else None.  PACKED_SLOT_BYTES gives the layer's slot size (0: the layer stays dense); the operand must be
+        bf16 [n, 256] on one GPU with dropout inactive, and the launch the wave-per-row kernel
+        (ops.spmm_packed_slot).  Full-graph steps only: never inside a stream capture."""
+        slot = PACKED_SLOT_BYTES[layer] if layer < len(PACKED_SLOT_BYTES) else 0
+        drop_on = self.training and self.dropout is not None and self.dropout > 0.0
+        if (not slot or drop_on or self._shard is not None or ops.K.name != "hip" or layer >= len(self.convs)
+                or self.convs[layer]._shard is not None or torch.cuda.is_current_stream_capturing()):
+            return None
+        if isinstance(edge_index, ops.CSRGraph):
+            graph = edge_index
+        elif torch.is_tensor(edge_index):
+            graph = ops.graph_cache.get(edge_index, n)
+        else:
+            return None
+        d = self.fcs[0].out_features
+        slot = ops.spmm_packed_slot(graph, (n, d), dtype, slot)
+        return {"slot_bytes": slot, "out": None} if slot else None
+
     def fused_stem_ok(self, x) -> bool:
         """SGFormer.forward may run this branch's stem Linear + BatchNorm + relu (and TransConv's stem Linear) as ONE
         autograd node (ops.stem_pair_bn) when the layers behind it are the fused ones and no dropout follows the stem."""
@@ -326,10 +357,14 @@ class GraphConv(nn.Module):
         `stem` (not in the reference signature): (fcs[0](x), its batch statistics or None), when SGFormer.forward
         has computed both branches' first Linear in one pass over x (ops.stem_pair)."""
         ops._require_cuda(x, None if isinstance(edge_index, ops.CSRGraph) else edge_index)
-        x_first = None
-        if stem is not None and len(stem) == 3:
-            # ("bn", x0, x0'): the stem ran as one node with its BatchNorm (ops.stem_pair_bn); x0' feeds the first SpMM
-            _, x, x_first = stem
+        x_first = packed = None
+        if stem is not None and len(stem) >= 3:
+            # ("bn", x0, x0'[, pack request]): the stem ran as one node with its BatchNorm (ops.stem_pair_bn); x0' feeds the
+            # first SpMM — from its packed copy when the node was asked for one (pack_request: the copy is in ["out"])
+            x, x_first = stem[1], stem[2]
+            # (taken OUT of the request: the copy, 0.94 GB at products size, lives until the first SpMM has read it, not
+            # until the forward returns)
+            packed = stem[3].pop("out", None) if len(stem) > 3 and stem[3] is not None else None
         else:
             if stem is not None:
                 x, stats0 = stem
@@ -343,9 +378,13 @@ class GraphConv(nn.Module):
                 x = x_first
             for i, conv in enumerate(self.convs):
                 bn = self.bns[i + 1]
-                y = conv.propagate(x, edge_index)
+                y = conv.propagate(x, edge_index, packed)
+                packed = None
+                # this layer's BatchNorm pass writes the next SpMM's operand: packed too, if that launch gathers it
+                req = self.pack_request(i + 1, x0.shape[0], x0.dtype, edge_index) if self.use_act else None
                 x = ops.linear_bn_act_res(y, x0, conv.W.weight, conv.W.bias, bn.weight, bn.bias, self._bn_hook(bn),
-                                          self.use_act, self.use_residual, self._shard, chain, i == 0)
+                                          self.use_act, self.use_residual, self._shard, chain, i == 0, req)
+                packed = req.pop("out", None) if req is not None else None
             return x
         # x0 = layer_[0] has up to 2 consumers per layer (the [. | x0] Linear and the residual) plus
         # the first SpMM: hand out aliases through a hub whose backward sums all their gradients in
@@ -658,9 +697,10 @@ class SGFormer(nn.Module):
             if getattr(tc, "use_bn", False) and hasattr(tc, "bns") and ops.stem_ln_supported(x, wt):
                 # TransConv's stem too: Linear -> LayerNorm -> relu in the same node (its dW comes from sgf_gram_ln_bwd)
                 ln = (tc.bns[0].weight, tc.bns[0].bias, tc.bns[0].eps, True)
+            req = gc.pack_request(0, x.shape[0], x.dtype, edge_index)
             x0a, x0b, yt = ops.stem_pair_bn(x, wg, gc.fcs[0].bias, wt, tc.fcs[0].bias,
-                                            bn0.weight, bn0.bias, gc._bn_hook(bn0), gc._shard, ln)
-            stem_t, stem_g = (("ln", yt) if ln is not None else yt), ("bn", x0a, x0b)
+                                            bn0.weight, bn0.bias, gc._bn_hook(bn0), gc._shard, ln, req)
+            stem_t, stem_g = (("ln", yt) if ln is not None else yt), ("bn", x0a, x0b, req)
         elif both and ops.stem_pair_supported(x, wg, wt):
             want = gc.use_bn and _uses_batch_stats(gc, gc.bns[0])
             (yg, yt), st = ops.stem_pair(x, wg, gc.fcs[0].bias, wt, tc.fcs[0].bias,
