@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 663 /* 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 664 /* 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -906,6 +906,17 @@ int sgf_gcn_epilogue_stats_add(const void* a, int64_t lda, const void* w, int64_
  * sgf_gcn_epilogue_workspace_bytes(n, d_out).
  * ------------------------------------------------------------------------------------------ */
 int32_t sgf_stem_pair_supported(int32_t d_in, int32_t d_out, int32_t dtype);
+/* Geometry of the persistent bf16 row kernels behind the T4 / T6 / T7 entries (host query, no GPU needed).  Every wave of a
+ * launch streams 32-row tiles t, t + waves, ...; the result is the number of rows ONE lap of all waves covers when the grid
+ * is at its cap: virtual blocks (the groups of 1, 2 or 4 workgroups that walk the same tiles) x waves per block x 32.  A
+ * launch over more than k times that many rows gives every wave more than k tiles.  kind, one per launch geometry:
+ *   0 sgf_gcn_epilogue_stats / _dx / _partial / _stats_add      4 sgf_gcn_epilogue_cat
+ *   1 sgf_gcn_epilogue_dx2 with pair != 0                       5 sgf_stem_pair (d = d_out)
+ *   2 sgf_gcn_epilogue_dx2_acc                                  6 sgf_combine_fc_fwd / _fwd_mapped
+ *   3 sgf_gcn_bn_bwd_dx                                         7 sgf_combine_fc_bwd / _bwd_mapped / _bwd_g
+ * d in {64, 128, 256} (kinds 6, 7: d % 32 == 0, d <= 256, at most 64 classes), dtype SGF_BF16; -1 for anything else (fp32
+ * storage runs other kernels: csrc/linear_f32.hip).  The entries size their grids with the functions this reads. */
+int32_t sgf_row_lap_rows(int32_t kind, int32_t d, int32_t dtype);
 int sgf_stem_pair(const void* x, int64_t ldx, int64_t n, int32_t d_in, const void* w0, int64_t ldw0,
                   const float* bias0, const void* w1, int64_t ldw1, const float* bias1, int32_t d_out, int32_t dtype,
                   void* y0, int64_t ldy0, void* y1, int64_t ldy1, const float* shift0, float* stats0, void* workspace,

@@ -193,6 +193,9 @@ __device__ __forceinline__ int mfma32_row(int r, int lane) {
   return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
 }
 
+// ---- rows one lap of all waves of the head kernels covers in a launch over n rows (csrc/head.hip; sgf_row_lap_rows) ----
+int64_t head_lap_rows(bool bwd, int64_t n);
+
 // ---- per-wave streaming row kernels of csrc/rowgemm.hip, used by csrc/attn.hip for the attention-from-input passes ----
 bool hrow_supported(int d, int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, const void* c, int64_t ldc,
                     const void* o, int64_t ldo);

@@ -287,12 +287,20 @@ __global__ __launch_bounds__(kHeadBwdThreads) void k_head_bwd_bf16(
   }
 }
 
+// launch geometry: workgroups of kHeadThreads / 64 (forward) and kHeadBwdThreads / 64 (backward) waves, a wave takes one
+// 32-row tile per lap; head_lap_rows (below) reports the same numbers to sgf_row_lap_rows
 inline int head_grid(int64_t n) {
   int64_t b = (n + 127) / 128;
   const int64_t cap = static_cast<int64_t>(kNumCU) * 4;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return static_cast<int>(b);
+}
+
+inline int head_bwd_grid(int64_t n) {
+  int64_t nb = ((n + 31) / 32 + kHeadBwdThreads / 64 - 1) / (kHeadBwdThreads / 64);
+  if (nb > kNumCU) nb = kNumCU;
+  return static_cast<int>(nb);
 }
 
 int check_head(const char* fn, int64_t n, int d, int c, int dtype) {
@@ -314,6 +322,12 @@ int check_head(const char* fn, int64_t n, int d, int c, int dtype) {
 }
 
 }  // namespace
+
+int64_t head_lap_rows(bool bwd, int64_t n) {
+  return bwd ? static_cast<int64_t>(head_bwd_grid(n)) * (kHeadBwdThreads / 64) * 32
+             : static_cast<int64_t>(head_grid(n)) * (kHeadThreads / 64) * 32;
+}
+
 }  // namespace sgf
 
 using namespace sgf;
@@ -404,9 +418,7 @@ static int combine_fc_bwd_impl(const char* fn, const float* dlogits, int64_t ldd
               SGF_E_INVALID, "%s: bad pointer / ld (dx1 / dx2: 16-byte aligned, ld %% 8 == 0)", fn);
   SGF_REQUIRE(n < (static_cast<int64_t>(1) << 31), SGF_E_UNSUPPORTED, "%s: more than 2^31 - 1 rows", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int64_t nb = ((n + 31) / 32 + kHeadBwdThreads / 64 - 1) / (kHeadBwdThreads / 64);
-  if (nb > kNumCU) nb = kNumCU;
-  const dim3 grid(static_cast<unsigned>(nb)), block(kHeadBwdThreads);
+  const dim3 grid(static_cast<unsigned>(head_bwd_grid(n))), block(kHeadBwdThreads);
 #define SGF_HEAD_BWD(DP_)                                                                                   \
   hipLaunchKernelGGL((k_head_bwd_bf16<DP_>), grid, block, 0, st, dlogits, lddl, w, n, d, classes, a, b,       \
                      static_cast<uint16_t*>(dx1), ld1, static_cast<uint16_t*>(dx2), ld2, rmap,                \

@@ -1469,6 +1469,36 @@ int grid_blocks(int64_t n) {
   return static_cast<int>(b);
 }
 
+// Launch geometry: the VIRTUAL blocks of a launch over n rows (a virtual block is the group of 1, 2 or 4 workgroups that walk
+// the same row tiles; each has kRgWaves waves, a wave takes one 32-row tile per lap).  One function per geometry; the
+// entries launch with them and sgf_row_lap_rows reports them at the grid cap, so the two cannot drift.
+// sgf_gcn_epilogue_stats / _dx / _partial / _stats_add and sgf_stem_pair: grid_blocks(n).
+int dx2_pair_vblocks(int64_t n) { return grid_blocks(n) / 16 * 8; }   // whole groups of 8 pairs = 16 consecutive blocks;
+                                                                      // 0: too few tiles, the entry runs two plain launches
+int dx2_acc_vblocks(int64_t n, int d) {
+  if (d != 256) return grid_blocks(n);
+  const int pairs = dx2_pair_vblocks(n);
+  return pairs < 8 ? 8 : pairs;
+}
+int bn_bwd_dx_vblocks(int64_t n, int d) {
+  const int roles = d / 64;
+  int vblocks = (grid_blocks(n) + roles - 1) / roles;
+  if (roles > 1) {
+    vblocks = (vblocks + 7) / 8 * 8;                   // whole groups of 8 tiles' worth of blocks: b, b + 8, ... share an XCD
+    if (vblocks > kNumCU / roles) vblocks = kNumCU / roles;
+  }
+  return vblocks;
+}
+int cat_vblocks(int64_t n, int d) {
+  int vblocks = grid_blocks(n);
+  if (d == 256) {                                      // whole groups of 8 pairs = 16 consecutive blocks
+    vblocks = (vblocks + 1) / 2;
+    vblocks = (vblocks + 7) / 8 * 8;
+    if (vblocks > kNumCU / 2) vblocks = kNumCU / 2;
+  }
+  return vblocks;
+}
+
 template <bool STATS, int IO>
 int launch_rowgemm(const RowGemmArgs& a, int d, int blocks, hipStream_t st) {
   switch (d) {
@@ -1585,6 +1615,27 @@ int hrow_bwd(const void* h, int64_t ldh, const void* g, int64_t ldg, const void*
 
 using namespace sgf;
 
+// Rows that one lap of all waves covers at the grid cap, for the bf16 streaming row kernels (include/sgf.h)
+extern "C" int32_t sgf_row_lap_rows(int32_t kind, int32_t d, int32_t dtype) {
+  if (dtype != SGF_BF16) return -1;
+  const int64_t cap_n = static_cast<int64_t>(1) << 40;   // any n beyond the grid cap
+  if (kind == 6 || kind == 7) {
+    if (d <= 0 || d % 32 != 0 || d > 256) return -1;
+    return static_cast<int32_t>(head_lap_rows(kind == 7, cap_n));
+  }
+  if (d != 64 && d != 128 && d != 256) return -1;
+  int vblocks;
+  switch (kind) {
+    case 0: case 5: vblocks = grid_blocks(cap_n); break;
+    case 1: vblocks = dx2_pair_vblocks(cap_n); break;
+    case 2: vblocks = dx2_acc_vblocks(cap_n, d); break;
+    case 3: vblocks = bn_bwd_dx_vblocks(cap_n, d); break;
+    case 4: vblocks = cat_vblocks(cap_n, d); break;
+    default: return -1;
+  }
+  return vblocks * kRgWaves * 32;
+}
+
 extern "C" int32_t sgf_gcn_epilogue_supported(int32_t d_in, int32_t d_out, int32_t dtype) {
   return supported(d_in, d_out, dtype) ? 1 : 0;
 }
@@ -1665,7 +1716,8 @@ extern "C" int sgf_gcn_epilogue_dx2(const void* dy, int64_t lddy, const void* w1
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (f32_storage(dtype) || !pair || grid_blocks(n) < 16) {
+  const int pairs = dx2_pair_vblocks(n);
+  if (f32_storage(dtype) || !pair || pairs == 0) {
     rc = sgf_gcn_epilogue_dx(dy, lddy, w1, ldw, n, d, d, dtype, dx1, lddx1, stream);
     if (rc != SGF_OK) return rc;
     return sgf_gcn_epilogue_dx(dy, lddy, w2, ldw, n, d, d, dtype, dx2, lddx2, stream);
@@ -1673,7 +1725,6 @@ extern "C" int sgf_gcn_epilogue_dx2(const void* dy, int64_t lddy, const void* w1
   RowGemmArgs args{static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(w1), ldw, 1, nullptr, nullptr,
                    nullptr, static_cast<uint16_t*>(dx1), lddx1, n, nullptr,
                    static_cast<const uint16_t*>(w2), static_cast<uint16_t*>(dx2), lddx2, 1};
-  const int pairs = grid_blocks(n) / 16 * 8;          // whole groups of 8 pairs = 16 consecutive blocks
   return launch_rowgemm<false, 0>(args, d, 2 * pairs, st);
 }
 
@@ -1700,14 +1751,13 @@ extern "C" int sgf_gcn_epilogue_dx2_acc(const void* dz, int64_t lddz, const void
   Dx2AccArgs a{static_cast<const uint16_t*>(dz), lddz, static_cast<const uint16_t*>(w), ldw, static_cast<uint16_t*>(dy), lddy,
                static_cast<const uint16_t*>(gadd), ldg, static_cast<const uint16_t*>(acc_in), ldai,
                static_cast<uint16_t*>(acc_out), ldao, n};
+  const int vblocks = dx2_acc_vblocks(n, d);
   if (d == 256) {
-    int pairs = grid_blocks(n) / 16 * 8;                // whole groups of 8 pairs = 16 consecutive blocks
-    if (pairs < 8) pairs = 8;
-    hipLaunchKernelGGL((k_dx2acc_bf16<256, 2>), dim3(2 * pairs), dim3(kRgThreads), 0, st, a);
+    hipLaunchKernelGGL((k_dx2acc_bf16<256, 2>), dim3(2 * vblocks), dim3(kRgThreads), 0, st, a);
   } else if (d == 128) {
-    hipLaunchKernelGGL((k_dx2acc_bf16<128, 1>), dim3(grid_blocks(n)), dim3(kRgThreads), 0, st, a);
+    hipLaunchKernelGGL((k_dx2acc_bf16<128, 1>), dim3(vblocks), dim3(kRgThreads), 0, st, a);
   } else {
-    hipLaunchKernelGGL((k_dx2acc_bf16<64, 1>), dim3(grid_blocks(n)), dim3(kRgThreads), 0, st, a);
+    hipLaunchKernelGGL((k_dx2acc_bf16<64, 1>), dim3(vblocks), dim3(kRgThreads), 0, st, a);
   }
   SGF_LAUNCH_CHECK();
   return SGF_OK;
@@ -1753,11 +1803,7 @@ extern "C" int sgf_gcn_bn_bwd_dx(const void* gy, int64_t ldg, const void* z, int
   SGF_REQUIRE((!acc_in || reinterpret_cast<uintptr_t>(acc_in) % 16 == 0) && (!acc_out || reinterpret_cast<uintptr_t>(acc_out) % 16 == 0),
               SGF_E_INVALID, "%s: running-sum buffers must be 16-byte aligned", fn);
   const int roles = d / 64;
-  int vblocks = (grid_blocks(n) + roles - 1) / roles;
-  if (roles > 1) {
-    vblocks = (vblocks + 7) / 8 * 8;                   // whole groups of 8 tiles' worth of blocks: b, b + 8, ... share an XCD
-    if (vblocks > kNumCU / roles) vblocks = kNumCU / roles;
-  }
+  const int vblocks = bn_bwd_dx_vblocks(n, d);
   BnBwdDxArgs a{static_cast<const uint16_t*>(gy), ldg, static_cast<const uint16_t*>(z), ldz, mean, rstd, gamma, beta,
                 stats, inv_n, training, relu, static_cast<const uint16_t*>(w), ldw, static_cast<uint16_t*>(dz), lddz,
                 static_cast<uint16_t*>(dy), lddy, static_cast<const uint4*>(acc_in), static_cast<uint4*>(acc_out),
@@ -1811,13 +1857,7 @@ extern "C" int sgf_gcn_epilogue_cat(const void* a1, int64_t lda1, const void* a2
   SGF_REQUIRE(lda1 >= d && lda2 >= d && ldy >= d && ldw >= 2 * d, SGF_E_INVALID, "%s: leading dimension smaller than the width", fn);
   SGF_REQUIRE(rows16(a1, lda1) && rows16(a2, lda2) && rows16(w, ldw) && rows16(y, ldy), SGF_E_INVALID,
               "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 8 elements)", fn);
-  const int roles = d == 256 ? 2 : 1;
-  int vblocks = grid_blocks(n);
-  if (roles == 2) {                                    // whole groups of 8 pairs = 16 consecutive blocks
-    vblocks = (vblocks + 1) / 2;
-    vblocks = (vblocks + 7) / 8 * 8;
-    if (vblocks > kNumCU / 2) vblocks = kNumCU / 2;
-  }
+  const int vblocks = cat_vblocks(n, d);
   RowGemm2Args args{static_cast<const uint16_t*>(a1), lda1, static_cast<const uint16_t*>(a2), lda2,
                     static_cast<const uint16_t*>(w), ldw, bias, shift, nullptr, static_cast<uint16_t*>(y), ldy, n};
   if (stats) {

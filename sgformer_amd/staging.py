@@ -71,8 +71,8 @@ class on_prep:
 
 def h2d(t: torch.Tensor, device) -> torch.Tensor:
     """`t.to(device)` for a host tensor, copied on the prep stream (the host waits for THAT stream only)."""
-    if t.is_cuda or not enabled() or torch.cuda.is_current_stream_capturing():
-        return t.to(device)
+    if t.is_cuda or torch.device(device).type != "cuda" or not enabled() or torch.cuda.is_current_stream_capturing():
+        return t.to(device)                              # (a host model on a machine that has a GPU: there is no stream to use)
     with on_prep(device) as hand_over:
         out = t.to(device)
         hand_over(out)
