@@ -1287,10 +1287,6 @@ inline int persistent_blocks(int64_t n, int R, int64_t cap = kMaxBlocks) {
   return static_cast<int>(ntiles < cap ? ntiles : cap);
 }
 
-// f(T{}) with the storage type of a checked dtype code: float for SGF_F32, uint16_t for SGF_BF16
-template <typename F>
-inline int by_dtype(int dtype, F&& f) { return dtype == SGF_F32 ? f(float{}) : f(uint16_t{}); }
-
 template <typename T, int MODE>
 int launch_reduce(const ReduceArgs& args, int DP, int nblk, hipStream_t st) {
   const dim3 grid(nblk, args.heads), block(sizeof(T) == 2 ? bf_reduce_waves(MODE) * 64 : kRedThreads);
@@ -1379,12 +1375,7 @@ int finalize_attn(const float* part, int nblk, int heads, int d, int DP, int RG,
   return SGF_OK;
 }
 
-// the empty sums (n == 0) of the reduce entries, and of the Gram entries: c and whichever of the m-vectors were asked for
-int zero_floats(float* p, int64_t len, hipStream_t st) {
-  SGF_CHECK_HIP(hipMemsetAsync(p, 0, len * sizeof(float), st));
-  return SGF_OK;
-}
-
+// the empty sums (n == 0) of the Gram entries: c and whichever of the m-vectors were asked for (the reduce entries: zero_floats)
 int zero_gram_outputs(float* c, int64_t ldc, int m, int k, std::initializer_list<float*> vectors, hipStream_t st) {
   SGF_CHECK_HIP(hipMemset2DAsync(c, ldc * sizeof(float), 0, k * sizeof(float), m, st));
   for (float* v : vectors)

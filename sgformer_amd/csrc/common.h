@@ -13,7 +13,7 @@
 namespace sgf {
 
 // ---- error reporting -----------------------------------------------------------------------
-void set_error(const char* fmt, ...);
+void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
 #define SGF_CHECK_HIP(expr)                                                              \
   do {                                                                                   \
@@ -212,6 +212,19 @@ int hrow_bwd(const void* h, int64_t ldh, const void* g, int64_t ldg, const void*
 
 // fp32 storage, whichever way its matrix products are formed (SGF_F32: exact; SGF_F32_BF16X3: three bf16 products)
 inline bool f32_storage(int dtype) { return dtype == SGF_F32 || dtype == SGF_F32_BF16X3; }
+
+// f(T{}) with the storage type of a checked dtype code: float for SGF_F32, uint16_t for SGF_BF16
+template <typename F>
+inline int by_dtype(int dtype, F&& f) { return dtype == SGF_F32 ? f(float{}) : f(uint16_t{}); }
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
+template <typename F>
+inline int by_flag(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// the empty sums (n == 0) of the entries that reduce over rows
+inline int zero_floats(float* p, int64_t len, hipStream_t st) {
+  SGF_CHECK_HIP(hipMemsetAsync(p, 0, len * sizeof(float), st));
+  return SGF_OK;
+}
 
 // ---- SGF_F32_BF16X3: an fp32 value as the sum of two bf16 values (csrc/linear_f32x.hip, csrc/gram_f32x.hip) -------------
 // hi = bf16_rne(a), lo = bf16_rne(a - hi) (the subtraction is exact in fp32); lo = 0 where hi is not finite, so that an

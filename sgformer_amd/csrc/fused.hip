@@ -1310,31 +1310,20 @@ __global__ __launch_bounds__(kThreads) void k_nll_bwd(const T* __restrict__ logi
   }
 }
 
-inline int ew_grid(int64_t total_vec) {
-  int64_t b = (total_vec + kThreads - 1) / kThreads;
-  const int64_t cap = static_cast<int64_t>(kNumCU) * 8;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
+// ---- host side: every entry is checks, one launch call and (for a column reduction) one sum_partials --------------------------
+// a persistent grid: `blocks` of them, at least 1 and at most `cap` (8 per CU unless the kernel leaves one partial row per block)
+inline int clamp_grid(int64_t blocks, int64_t cap = static_cast<int64_t>(kNumCU) * 8) {
+  return static_cast<int>(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
 }
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline int ew_grid(int64_t total_vec) { return clamp_grid(ceil_div(total_vec, kThreads)); }
 
 // blocks for the column-fixed row-walk kernels: enough to fill the chip (8 blocks / CU), never more
 // than one unrolled pass of rows per block
-inline int rowwalk_grid(int64_t n, int d) {
-  const int rpp = kThreads / (d / 4);
-  int64_t b = (n + static_cast<int64_t>(rpp) * kRowUnroll - 1) / (static_cast<int64_t>(rpp) * kRowUnroll);
-  const int64_t cap = static_cast<int64_t>(kNumCU) * 8;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
-}
+inline int rowwalk_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, static_cast<int64_t>(kThreads / (d / 4)) * kRowUnroll)); }
 
-inline int stat_blocks(int64_t n) {
-  int64_t b = (n + 63) / 64;  // >= 64 rows per block
-  if (b > kMaxStatBlocks) b = kMaxStatBlocks;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
-}
+inline int stat_blocks(int64_t n) { return clamp_grid(ceil_div(n, 64), kMaxStatBlocks); }  // >= 64 rows per block
 
 int check_ew(const char* fn, int64_t n, int d, int dtype) {
   SGF_REQUIRE(n >= 0 && d >= 1, SGF_E_INVALID, "%s: bad sizes n=%lld d=%d", fn,
@@ -1346,97 +1335,81 @@ int check_ew(const char* fn, int64_t n, int d, int dtype) {
   return SGF_OK;
 }
 
-template <typename T, typename... Args>
-int launch_ln_fwd(int lpr, int nc, dim3 grid, hipStream_t st, Args... args) {
-#define SGF_LN(L, C)                                                                   \
-  if (lpr == L && nc == C) {                                                           \
-    hipLaunchKernelGGL((k_ln_fwd<T, L, C>), grid, dim3(kThreads), 0, st, args...);     \
-    SGF_LAUNCH_CHECK();                                                                \
-    return SGF_OK;                                                                     \
-  }
-  SGF_LN(16, 1) SGF_LN(32, 1) SGF_LN(64, 1) SGF_LN(64, 2) SGF_LN(64, 3) SGF_LN(64, 4)
-#undef SGF_LN
-  set_error("sgf_ln_fwd: no kernel for lpr=%d nc=%d", lpr, nc);
-  return SGF_E_UNSUPPORTED;
-}
-template <typename T, typename... Args>
-int launch_ln_bwd(int lpr, int nc, dim3 grid, hipStream_t st, Args... args) {
-#define SGF_LN(L, C)                                                                   \
-  if (lpr == L && nc == C) {                                                           \
-    hipLaunchKernelGGL((k_ln_bwd<T, L, C>), grid, dim3(kThreads), 0, st, args...);     \
-    SGF_LAUNCH_CHECK();                                                                \
-    return SGF_OK;                                                                     \
-  }
-  SGF_LN(16, 1) SGF_LN(32, 1) SGF_LN(64, 1) SGF_LN(64, 2) SGF_LN(64, 3) SGF_LN(64, 4)
-#undef SGF_LN
-  set_error("sgf_ln_bwd: no kernel for lpr=%d nc=%d", lpr, nc);
-  return SGF_E_UNSUPPORTED;
+// kernel<<<grid, kThreads, 0, st>>>(args...), each argument cast to the kernel's parameter type (the entries hold their
+// operands as void*; a cast that static_cast refuses, such as float* to uint16_t*, does not compile)
+template <typename... Params, typename... Args>
+int launch(void (*kernel)(Params...), dim3 grid, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, static_cast<Params>(args)...);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
 }
 
-inline int ln_grid(int64_t n, int lpr) {
-  const int rpb = kThreads / lpr;
-  int64_t b = (n + rpb - 1) / rpb;
-  const int64_t cap = static_cast<int64_t>(kNumCU) * 8;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
+// out0[c] = Σ_blocks part[b][c] for c < split, out1[c - split] beyond it (either may be null), in fixed order
+int sum_partials(const float* part, int nblk, int width, float* out0, float* out1, int split, hipStream_t st) {
+  return launch(k_sum_partials, dim3((width + 7) / 8), st, part, nblk, width, out0, out1, split);
 }
-inline int ln_bwd_grid(int64_t n, int lpr) {
-  const int rpb = kThreads / lpr;
-  int64_t b = (n + rpb - 1) / rpb;
-  if (b > kMaxStatBlocks) b = kMaxStatBlocks;
-  if (b < 1) b = 1;
-  return static_cast<int>(b);
+
+// the LayerNorm kernels by (lanes per row, 4-column chunks per lane); Kernel::get<T, L, C>() is k_ln_fwd or k_ln_bwd
+struct LnFwd {
+  static constexpr const char* name = "sgf_ln_fwd";
+  template <typename T, int L, int C> static constexpr auto get() { return k_ln_fwd<T, L, C>; }
+};
+struct LnBwd {
+  static constexpr const char* name = "sgf_ln_bwd";
+  template <typename T, int L, int C> static constexpr auto get() { return k_ln_bwd<T, L, C>; }
+};
+template <typename Kernel, typename T, typename... Args>
+int launch_ln(int lpr, int nc, dim3 grid, hipStream_t st, Args... args) {
+#define SGF_LN(L, C) \
+  if (lpr == L && nc == C) return launch(Kernel::template get<T, L, C>(), grid, st, args...);
+  SGF_LN(16, 1) SGF_LN(32, 1) SGF_LN(64, 1) SGF_LN(64, 2) SGF_LN(64, 3) SGF_LN(64, 4)
+#undef SGF_LN
+  set_error("%s: no kernel for lpr=%d nc=%d", Kernel::name, lpr, nc);
+  return SGF_E_UNSUPPORTED;
 }
 
 // bf16 rows the 16-byte-per-lane kernels take: d a multiple of 8 with at most kThreads chunks, every row 16-byte aligned
 // (SGF_EW8=0: the 8-byte kernels, for A/B)
-inline bool ew8_rows(int d, std::initializer_list<std::pair<const void*, int64_t>> ops) {
-  static EnvInt ew8{"SGF_EW8", 1};
-  if (ew8.get() == 0 || d % 8 != 0 || d / 8 > kThreads) return false;
+inline bool rows16(std::initializer_list<std::pair<const void*, int64_t>> ops) {
   for (const auto& o : ops)
     if (o.first && (reinterpret_cast<uintptr_t>(o.first) % 16 != 0 || o.second % 8 != 0)) return false;
   return true;
 }
+inline bool ew8_rows(int d, std::initializer_list<std::pair<const void*, int64_t>> ops) {
+  static EnvInt ew8{"SGF_EW8", 1};
+  return ew8.get() != 0 && d % 8 == 0 && d / 8 <= kThreads && rows16(ops);
+}
 constexpr int kEw8Unroll = 4;   // rows in flight per lane (2 / 4 / 8 measured 0.77 / 0.71 / 0.70 ms on the 2R:1W apply; 8 loses on the statistics)
-inline int rowwalk8_grid(int64_t n, int d) {
-  const int64_t rpb = static_cast<int64_t>(kThreads / (d / 8)) * kEw8Unroll;
-  int64_t b = (n + rpb - 1) / rpb;
-  const int64_t cap = static_cast<int64_t>(kNumCU) * 8;
-  return static_cast<int>(b > cap ? cap : (b < 1 ? 1 : b));
+inline int rowwalk8_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, static_cast<int64_t>(kThreads / (d / 8)) * kEw8Unroll)); }
+
+// the 16-byte LayerNorm kernels: d in {64, 128, 256, 512}, one lane per 8 columns; f gets the lanes per row as an integral_constant
+inline bool ln8_width(int d) { return d == 64 || d == 128 || d == 256 || d == 512; }
+template <typename F>
+int by_ln8_lanes(int d, F&& f) {
+  switch (d / 8) {
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
 }
 
 template <typename T>
 int ln_fwd_t(const void* x, int64_t ldx, const void* res, int64_t ldr, float a, float b,
              const float* gamma, const float* beta, int relu, float eps, int64_t n, int d, void* y,
              int64_t ldy, float* mean, float* rstd, hipStream_t st) {
-  if (sizeof(T) == 2 && (d == 64 || d == 128 || d == 256 || d == 512) && ldx % 8 == 0 && ldy % 8 == 0 &&
-      (!res || ldr % 8 == 0) && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0 &&
-      (!res || reinterpret_cast<uintptr_t>(res) % 16 == 0)) {
+  if (sizeof(T) == 2 && ln8_width(d) && rows16({{x, ldx}, {y, ldy}, {res, ldr}})) {   // (not under SGF_EW8)
     constexpr int R = 4;
-    const int l8 = d / 8;
-    const int rpb = kThreads / l8 * R;
-    int64_t nb = (n + rpb - 1) / rpb;
-    if (nb > static_cast<int64_t>(kNumCU) * 8) nb = static_cast<int64_t>(kNumCU) * 8;
-    const dim3 grid(static_cast<unsigned>(nb < 1 ? 1 : nb));
-    const uint16_t* x16 = static_cast<const uint16_t*>(x);
-    const uint16_t* r16 = static_cast<const uint16_t*>(res);
-    uint16_t* y16 = static_cast<uint16_t*>(y);
-#define SGF_LN8(L) hipLaunchKernelGGL((k_ln_fwd_bf16x8<L, R>), grid, dim3(kThreads), 0, st, x16, ldx, r16, ldr, a, b, \
-                                      gamma, beta, relu, eps, n, y16, ldy, mean, rstd)
-    if (l8 == 8) SGF_LN8(8);
-    else if (l8 == 16) SGF_LN8(16);
-    else if (l8 == 32) SGF_LN8(32);
-    else SGF_LN8(64);
-#undef SGF_LN8
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    const dim3 grid(clamp_grid(ceil_div(n, kThreads / (d / 8) * R)));
+    return by_ln8_lanes(d, [&](auto l) {
+      return launch(k_ln_fwd_bf16x8<decltype(l)::value, R>, grid, st, x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, y,
+                    ldy, mean, rstd);
+    });
   }
   const int lpr = lanes_per_row(d);
   const int nc = (d + 4 * lpr - 1) / (4 * lpr);
-  return launch_ln_fwd<T>(lpr, nc, dim3(ln_grid(n, lpr)), st, static_cast<const T*>(x), ldx,
-                          static_cast<const T*>(res), ldr, a, b, gamma, beta, relu, eps, n, d,
-                          static_cast<T*>(y), ldy, mean, rstd);
+  return launch_ln<LnFwd, T>(lpr, nc, dim3(clamp_grid(ceil_div(n, kThreads / lpr))), st, x, ldx, res, ldr, a, b, gamma, beta,
+                             relu, eps, n, d, y, ldy, mean, rstd);
 }
 
 template <typename T>
@@ -1445,60 +1418,40 @@ int ln_bwd_t(const void* dy, int64_t lddy, const void* y, int64_t ldy, const voi
              const float* mean, const float* rstd, int64_t n, int d, void* dx, int64_t lddx,
              void* dres, int64_t lddres, float* dgamma, float* dbeta, void* ws, hipStream_t st) {
   float* part = static_cast<float*>(ws);
-  if (sizeof(T) == 2 && (d == 64 || d == 128 || d == 256 || d == 512) &&
+  int nblk, rc;
+  if (sizeof(T) == 2 && ln8_width(d) &&
       ew8_rows(d, {{dy, lddy}, {relu ? y : nullptr, ldy}, {gamma ? x : nullptr, ldx}, {gamma ? res : nullptr, ldr}, {dx, lddx},
                    {dres, lddres}})) {
     constexpr int R = 4;                                   // (2 / 4 / 8 rows in flight per lane measured 1.26 / 1.20 / 1.22 ms)
-    const int l8 = d / 8;
-    const int rpb = kThreads / l8 * R;
-    int64_t nb = (n + rpb - 1) / rpb;
-    if (nb > kMaxStatBlocks) nb = kMaxStatBlocks;
-    const int nblk8 = static_cast<int>(nb < 1 ? 1 : nb);
-#define SGF_LNB8R(L, R_)                                                                                               \
-  hipLaunchKernelGGL((k_ln_bwd_bf16x8<L, R_>), dim3(nblk8), dim3(kThreads), 0, st, static_cast<const uint16_t*>(dy), lddy, \
-                     static_cast<const uint16_t*>(y), ldy, static_cast<const uint16_t*>(x), ldx,                        \
-                     static_cast<const uint16_t*>(res), ldr, a, b, gamma, relu, mean, rstd, n, static_cast<uint16_t*>(dx), \
-                     lddx, static_cast<uint16_t*>(dres), lddres, part)
-#define SGF_LNB8(L) SGF_LNB8R(L, R)
-    if (l8 == 8) SGF_LNB8(8);
-    else if (l8 == 16) SGF_LNB8(16);
-    else if (l8 == 32) SGF_LNB8(32);
-    else SGF_LNB8(64);
-#undef SGF_LNB8R
-#undef SGF_LNB8
-    SGF_LAUNCH_CHECK();
-    if (gamma != nullptr && (dgamma || dbeta)) {
-      hipLaunchKernelGGL(k_sum_partials, dim3((2 * d + 7) / 8), dim3(256), 0, st, part, nblk8, 2 * d, dgamma, dbeta, d);
-      SGF_LAUNCH_CHECK();
-    }
-    return SGF_OK;
+    nblk = clamp_grid(ceil_div(n, kThreads / (d / 8) * R), kMaxStatBlocks);
+    rc = by_ln8_lanes(d, [&](auto l) {
+      return launch(k_ln_bwd_bf16x8<decltype(l)::value, R>, dim3(nblk), st, dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma,
+                    relu, mean, rstd, n, dx, lddx, dres, lddres, part);
+    });
+  } else {
+    const int lpr = lanes_per_row(d);
+    const int nc = (d + 4 * lpr - 1) / (4 * lpr);
+    nblk = clamp_grid(ceil_div(n, kThreads / lpr), kMaxStatBlocks);
+    rc = launch_ln<LnBwd, T>(lpr, nc, dim3(nblk), st, dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma, relu, mean, rstd, n, d,
+                             dx, lddx, dres, lddres, part);
   }
-  const int lpr = lanes_per_row(d);
-  const int nc = (d + 4 * lpr - 1) / (4 * lpr);
-  const int nblk = ln_bwd_grid(n, lpr);
-  int rc = launch_ln_bwd<T>(lpr, nc, dim3(nblk), st, static_cast<const T*>(dy), lddy,
-                            static_cast<const T*>(y), ldy, static_cast<const T*>(x), ldx,
-                            static_cast<const T*>(res), ldr, a, b, gamma, relu, mean, rstd, n, d,
-                            static_cast<T*>(dx), lddx, static_cast<T*>(dres), lddres, part);
-  if (rc != SGF_OK) return rc;
-  if (gamma != nullptr && (dgamma || dbeta)) {
-    hipLaunchKernelGGL(k_sum_partials, dim3((2 * d + 7) / 8), dim3(256), 0, st, part, nblk,
-                       2 * d, dgamma, dbeta, d);
-    SGF_LAUNCH_CHECK();
-  }
-  return SGF_OK;
+  if (rc != SGF_OK || !gamma || !(dgamma || dbeta)) return rc;
+  return sum_partials(part, nblk, 2 * d, dgamma, dbeta, d, st);
 }
 
 template <typename F>
 int colreduce(F f, int64_t n, int d, float* stats, void* ws, hipStream_t st) {
   const int nblk = stat_blocks(n);
-  float* part = static_cast<float*>(ws);
-  hipLaunchKernelGGL((k_colreduce<F>), dim3(nblk), dim3(kThreads), 0, st, f, n, d, part);
-  SGF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sum_partials, dim3((2 * d + 7) / 8), dim3(256), 0, st, part, nblk, 2 * d,
-                     stats, stats + d, d);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  const int rc = launch(k_colreduce<F>, dim3(nblk), st, f, n, d, ws);
+  return rc != SGF_OK ? rc : sum_partials(static_cast<float*>(ws), nblk, 2 * d, stats, stats + d, d, st);
+}
+
+// f(TS{}, TD{}, TI{}): the storage types of a row copy and of its index (int64_t or int32_t)
+template <typename F>
+int by_copy_types(int src_dtype, int dst_dtype, bool idx64, F&& f) {
+  return by_dtype(src_dtype, [&](auto ts) {
+    return by_dtype(dst_dtype, [&](auto td) { return idx64 ? f(ts, td, int64_t{}) : f(ts, td, int32_t{}); });
+  });
 }
 
 }  // namespace
@@ -1511,15 +1464,14 @@ extern "C" int sgf_ln_fwd(const void* x, int64_t ldx, const void* res, int64_t l
                           int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy, float* mean,
                           float* rstd, void* stream) {
   int rc = check_ew("sgf_ln_fwd", n, d, dtype);
-  if (rc != SGF_OK) return rc;
-  if (n == 0) return SGF_OK;
+  if (rc != SGF_OK || n == 0) return rc;
   SGF_REQUIRE(x && y && (!gamma || (beta && mean && rstd)), SGF_E_INVALID, "sgf_ln_fwd: null pointer");
   SGF_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && (!res || ldr % 4 == 0), SGF_E_INVALID,
               "sgf_ln_fwd: leading dims must be multiples of 4");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == SGF_F32)
-    return ln_fwd_t<float>(x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, d, y, ldy, mean, rstd, st);
-  return ln_fwd_t<uint16_t>(x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, d, y, ldy, mean, rstd, st);
+  return by_dtype(dtype, [&](auto t) {
+    return ln_fwd_t<decltype(t)>(x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, d, y, ldy, mean, rstd, st);
+  });
 }
 
 extern "C" size_t sgf_ln_bwd_workspace_bytes(int64_t n, int32_t d) {
@@ -1538,19 +1490,17 @@ extern "C" int sgf_ln_bwd(const void* dy, int64_t lddy, const void* y, int64_t l
   if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
-    if (gamma && dgamma) SGF_CHECK_HIP(hipMemsetAsync(dgamma, 0, d * sizeof(float), st));
-    if (gamma && dbeta) SGF_CHECK_HIP(hipMemsetAsync(dbeta, 0, d * sizeof(float), st));
-    return SGF_OK;
+    if (gamma && dgamma && (rc = zero_floats(dgamma, d, st)) != SGF_OK) return rc;
+    return gamma && dbeta ? zero_floats(dbeta, d, st) : SGF_OK;
   }
   SGF_REQUIRE(dy && dx && (!relu || y) && (!gamma || (x && mean && rstd)), SGF_E_INVALID,
               "sgf_ln_bwd: null pointer");
   SGF_REQUIRE(!gamma || (workspace && workspace_bytes >= sgf_ln_bwd_workspace_bytes(n, d)),
               SGF_E_WORKSPACE, "sgf_ln_bwd: workspace too small");
-  if (dtype == SGF_F32)
-    return ln_bwd_t<float>(dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma, relu, mean, rstd, n, d,
-                           dx, lddx, dres, lddres, dgamma, dbeta, workspace, st);
-  return ln_bwd_t<uint16_t>(dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma, relu, mean, rstd, n, d,
-                            dx, lddx, dres, lddres, dgamma, dbeta, workspace, st);
+  return by_dtype(dtype, [&](auto t) {
+    return ln_bwd_t<decltype(t)>(dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma, relu, mean, rstd, n, d, dx, lddx, dres,
+                                 lddres, dgamma, dbeta, workspace, st);
+  });
 }
 
 extern "C" size_t sgf_colstats_workspace_bytes(int64_t n, int32_t d) {
@@ -1566,18 +1516,14 @@ extern "C" int sgf_colstats(const void* x, int64_t ldx, const float* shift, int6
   if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   SGF_REQUIRE(stats, SGF_E_INVALID, "sgf_colstats: null stats");
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * d * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_floats(stats, 2 * d, st);
   SGF_REQUIRE(x && ldx % 4 == 0, SGF_E_INVALID, "sgf_colstats: bad x / ldx");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_colstats_workspace_bytes(n, d), SGF_E_WORKSPACE,
               "sgf_colstats: workspace too small");
-  if (dtype == SGF_F32)
-    return colreduce(ColStatsF<float>{static_cast<const float*>(x), ldx, shift}, n, d, stats,
-                     workspace, st);
-  return colreduce(ColStatsF<uint16_t>{static_cast<const uint16_t*>(x), ldx, shift}, n, d, stats,
-                   workspace, st);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return colreduce(ColStatsF<T>{static_cast<const T*>(x), ldx, shift}, n, d, stats, workspace, st);
+  });
 }
 
 // BatchNorm's per-column bookkeeping between its two passes, in ONE launch (it was ~14 tiny ATen launches per BatchNorm
@@ -1604,10 +1550,8 @@ extern "C" int sgf_bn_finalize(const float* sums, const float* shift, double n_t
   SGF_REQUIRE(sums && mean && rstd, SGF_E_INVALID, "sgf_bn_finalize: null pointer");
   const double nn = n_total > 1.0 ? n_total : 1.0;
   const float unbias = static_cast<float>(n_total / (n_total - 1.0 > 1.0 ? n_total - 1.0 : 1.0));
-  hipLaunchKernelGGL(k_bn_finalize, dim3((d + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), sums, shift,
-                     static_cast<float>(1.0 / nn), unbias, eps, momentum, running_mean, running_var, d, mean, rstd);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return launch(k_bn_finalize, dim3((d + 255) / 256), static_cast<hipStream_t>(stream), sums, shift,
+                static_cast<float>(1.0 / nn), unbias, eps, momentum, running_mean, running_var, d, mean, rstd);
 }
 
 extern "C" int sgf_bn_apply(const void* x, int64_t ldx, const float* mean, const float* rstd,
@@ -1615,35 +1559,20 @@ extern "C" int sgf_bn_apply(const void* x, int64_t ldx, const float* mean, const
                             int32_t relu, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
                             void* stream) {
   int rc = check_ew("sgf_bn_apply", n, d, dtype);
-  if (rc != SGF_OK) return rc;
-  if (n == 0) return SGF_OK;
+  if (rc != SGF_OK || n == 0) return rc;
   SGF_REQUIRE(x && y && mean && rstd, SGF_E_INVALID, "sgf_bn_apply: null pointer");
   SGF_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && (!res || ldr % 4 == 0), SGF_E_INVALID,
               "sgf_bn_apply: leading dims must be multiples of 4");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnParams p{mean, rstd, gamma, beta};
-  if (dtype == SGF_BF16 && ew8_rows(d, {{x, ldx}, {res, ldr}, {y, ldy}})) {
-    const dim3 g8(rowwalk8_grid(n, d));
-#define SGF_BNA(RES_, U_)                                                                                             \
-  hipLaunchKernelGGL((k_bn_apply_bf16x8<RES_, U_>), g8, dim3(kThreads), 0, st, static_cast<const uint16_t*>(x), ldx, p, \
-                     static_cast<const uint16_t*>(res), ldr, relu, n, d, static_cast<uint16_t*>(y), ldy)
-    if (res) SGF_BNA(true, kEw8Unroll);
-    else SGF_BNA(false, kEw8Unroll);
-#undef SGF_BNA
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
-  }
-  const dim3 grid(rowwalk_grid(n, d));
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_bn_apply<float>), grid, dim3(kThreads), 0, st,
-                       static_cast<const float*>(x), ldx, p, static_cast<const float*>(res), ldr,
-                       relu, n, d, static_cast<float*>(y), ldy);
-  else
-    hipLaunchKernelGGL((k_bn_apply<uint16_t>), grid, dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(x), ldx, p, static_cast<const uint16_t*>(res),
-                       ldr, relu, n, d, static_cast<uint16_t*>(y), ldy);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  if (dtype == SGF_BF16 && ew8_rows(d, {{x, ldx}, {res, ldr}, {y, ldy}}))
+    return by_flag(res, [&](auto r) {
+      return launch(k_bn_apply_bf16x8<decltype(r)::value, kEw8Unroll>, dim3(rowwalk8_grid(n, d)), st, x, ldx, p, res, ldr, relu,
+                    n, d, y, ldy);
+    });
+  return by_dtype(dtype, [&](auto t) {
+    return launch(k_bn_apply<decltype(t)>, dim3(rowwalk_grid(n, d)), st, x, ldx, p, res, ldr, relu, n, d, y, ldy);
+  });
 }
 
 extern "C" int sgf_bn_apply_packed(const void* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
@@ -1656,29 +1585,20 @@ extern "C" int sgf_bn_apply_packed(const void* x, int64_t ldx, const float* mean
   if (rc != SGF_OK) return rc;
   SGF_REQUIRE(dtype == SGF_BF16 && d == 256, SGF_E_UNSUPPORTED, "%s: packed rows are bf16 rows of 256 columns", fn);
   SGF_REQUIRE(slot_bytes == 384 || slot_bytes == 448, SGF_E_UNSUPPORTED, "%s: slot_bytes must be 384 or 448", fn);
-  SGF_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && (!res || ldr % 8 == 0) && reinterpret_cast<uintptr_t>(x) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(y) % 16 == 0 && (!res || reinterpret_cast<uintptr_t>(res) % 16 == 0) &&
-                  reinterpret_cast<uintptr_t>(packed) % 128 == 0,
-              SGF_E_INVALID, "%s: rows must be 16-byte aligned, the packed buffer 128-byte aligned", fn);
+  SGF_REQUIRE(rows16({{x, ldx}, {y, ldy}, {res, ldr}}) && reinterpret_cast<uintptr_t>(packed) % 128 == 0, SGF_E_INVALID,
+              "%s: rows must be 16-byte aligned, the packed buffer 128-byte aligned", fn);
   hipStream_t st = static_cast<hipStream_t>(stream);
   SGF_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), st));
   if (n == 0) return SGF_OK;
   const BnParams p{mean, rstd, gamma, beta};
   const dim3 g8(rowwalk8_grid(n, d));
-#define SGF_BNP(RES_, S_)                                                                                                 \
-  hipLaunchKernelGGL((k_bn_apply_bf16x8_packed<RES_, kEw8Unroll, S_>), g8, dim3(kThreads), 0, st,                         \
-                     static_cast<const uint16_t*>(x), ldx, p, static_cast<const uint16_t*>(res), ldr, relu, n,            \
-                     static_cast<uint16_t*>(y), ldy, static_cast<uint4*>(packed), overflow)
-  if (res) {
-    if (slot_bytes == 384) SGF_BNP(true, 384);
-    else SGF_BNP(true, 448);
-  } else {
-    if (slot_bytes == 384) SGF_BNP(false, 384);
-    else SGF_BNP(false, 448);
-  }
-#undef SGF_BNP
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_flag(res, [&](auto r) {
+    auto go = [&](auto slot) {
+      return launch(k_bn_apply_bf16x8_packed<decltype(r)::value, kEw8Unroll, decltype(slot)::value>, g8, st, x, ldx, p, res, ldr,
+                    relu, n, y, ldy, packed, overflow);
+    };
+    return slot_bytes == 384 ? go(std::integral_constant<int, 384>{}) : go(std::integral_constant<int, 448>{});
+  });
 }
 
 extern "C" int sgf_bn_bwd_stats2(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* x, int64_t ldx,
@@ -1689,10 +1609,7 @@ extern "C" int sgf_bn_bwd_stats2(const void* dy, int64_t lddy, const void* dy2, 
   if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   SGF_REQUIRE(stats, SGF_E_INVALID, "sgf_bn_bwd_stats2: null stats");
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * d * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_floats(stats, 2 * d, st);
   SGF_REQUIRE(dy && x && mean && rstd && lddy % 4 == 0 && ldx % 4 == 0 && (!dy2 || lddy2 % 4 == 0), SGF_E_INVALID,
               "sgf_bn_bwd_stats2: bad pointer / ld");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_colstats_workspace_bytes(n, d), SGF_E_WORKSPACE,
@@ -1700,25 +1617,18 @@ extern "C" int sgf_bn_bwd_stats2(const void* dy, int64_t lddy, const void* dy2, 
   const BnParams p{mean, rstd, gamma, beta};
   if (dtype == SGF_BF16 && ew8_rows(d, {{dy, lddy}, {dy2, lddy2}, {x, ldx}})) {
     const int nblk = stat_blocks(n);
-    float* part = static_cast<float*>(workspace);
-#define SGF_BNS(TWO_, U_)                                                                                             \
-  hipLaunchKernelGGL((k_bn_bwd_stats_bf16x8<TWO_, U_>), dim3(nblk), dim3(kThreads), 0, st, static_cast<const uint16_t*>(dy), \
-                     lddy, static_cast<const uint16_t*>(dy2), lddy2, static_cast<const uint16_t*>(x), ldx, p, relu, n, d, part)
-    if (dy2) SGF_BNS(true, kEw8Unroll);
-    else SGF_BNS(false, kEw8Unroll);
-#undef SGF_BNS
-    SGF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sum_partials, dim3((2 * d + 7) / 8), dim3(256), 0, st, part, nblk, 2 * d, stats, stats + d, d);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
+    rc = by_flag(dy2, [&](auto two) {
+      return launch(k_bn_bwd_stats_bf16x8<decltype(two)::value, kEw8Unroll>, dim3(nblk), st, dy, lddy, dy2, lddy2, x, ldx, p,
+                    relu, n, d, workspace);
+    });
+    return rc != SGF_OK ? rc : sum_partials(static_cast<float*>(workspace), nblk, 2 * d, stats, stats + d, d, st);
   }
-  if (dtype == SGF_F32)
-    return colreduce(BnBwdStatsF<float>{static_cast<const float*>(dy), lddy, static_cast<const float*>(x), ldx, p, relu,
-                                        static_cast<const float*>(dy2), lddy2},
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return colreduce(BnBwdStatsF<T>{static_cast<const T*>(dy), lddy, static_cast<const T*>(x), ldx, p, relu,
+                                    static_cast<const T*>(dy2), lddy2},
                      n, d, stats, workspace, st);
-  return colreduce(BnBwdStatsF<uint16_t>{static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(x), ldx, p,
-                                         relu, static_cast<const uint16_t*>(dy2), lddy2},
-                   n, d, stats, workspace, st);
+  });
 }
 
 extern "C" int sgf_bn_bwd_stats(const void* dy, int64_t lddy, const void* x, int64_t ldx,
@@ -1736,55 +1646,32 @@ extern "C" int sgf_bn_bwd_apply(const void* dy, int64_t lddy, const void* x, int
                                 int32_t training, int64_t n, int32_t d, int32_t dtype, void* dx,
                                 int64_t lddx, void* stream) {
   int rc = check_ew("sgf_bn_bwd_apply", n, d, dtype);
-  if (rc != SGF_OK) return rc;
-  if (n == 0) return SGF_OK;
+  if (rc != SGF_OK || n == 0) return rc;
   SGF_REQUIRE(dy && x && dx && mean && rstd && (!training || stats), SGF_E_INVALID,
               "sgf_bn_bwd_apply: null pointer");
   SGF_REQUIRE(lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, SGF_E_INVALID,
               "sgf_bn_bwd_apply: leading dims must be multiples of 4");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const BnParams p{mean, rstd, gamma, beta};
-  if (dtype == SGF_BF16 && ew8_rows(d, {{dy, lddy}, {x, ldx}, {dx, lddx}})) {
-#define SGF_BNB(U_)                                                                                                   \
-  hipLaunchKernelGGL((k_bn_bwd_apply_bf16x8<U_>), dim3(rowwalk8_grid(n, d)), dim3(kThreads), 0, st,                     \
-                     static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(x), ldx, p, relu, stats, inv_n, \
-                     training, n, d, static_cast<uint16_t*>(dx), lddx)
-    SGF_BNB(kEw8Unroll);
-#undef SGF_BNB
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
-  }
-  const dim3 grid(rowwalk_grid(n, d));
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_bn_bwd_apply<float>), grid, dim3(kThreads), 0, st,
-                       static_cast<const float*>(dy), lddy, static_cast<const float*>(x), ldx, p,
-                       relu, stats, inv_n, training, n, d, static_cast<float*>(dx), lddx);
-  else
-    hipLaunchKernelGGL((k_bn_bwd_apply<uint16_t>), grid, dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(x), ldx,
-                       p, relu, stats, inv_n, training, n, d, static_cast<uint16_t*>(dx), lddx);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  if (dtype == SGF_BF16 && ew8_rows(d, {{dy, lddy}, {x, ldx}, {dx, lddx}}))
+    return launch(k_bn_bwd_apply_bf16x8<kEw8Unroll>, dim3(rowwalk8_grid(n, d)), st, dy, lddy, x, ldx, p, relu, stats, inv_n,
+                  training, n, d, dx, lddx);
+  return by_dtype(dtype, [&](auto t) {
+    return launch(k_bn_bwd_apply<decltype(t)>, dim3(rowwalk_grid(n, d)), st, dy, lddy, x, ldx, p, relu, stats, inv_n, training,
+                  n, d, dx, lddx);
+  });
 }
 
 extern "C" int sgf_axpby(const void* x1, int64_t ld1, float a, const void* x2, int64_t ld2, float b,
                          int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy, void* stream) {
   int rc = check_ew("sgf_axpby", n, d, dtype);
-  if (rc != SGF_OK) return rc;
-  if (n == 0) return SGF_OK;
+  if (rc != SGF_OK || n == 0) return rc;
   SGF_REQUIRE(x1 && x2 && y && ld1 % 4 == 0 && ld2 % 4 == 0 && ldy % 4 == 0, SGF_E_INVALID,
               "sgf_axpby: bad pointer / ld");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(ew_grid(n * (d / 4)));
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_axpby<float>), grid, dim3(kThreads), 0, st, static_cast<const float*>(x1),
-                       ld1, a, static_cast<const float*>(x2), ld2, b, n, d, static_cast<float*>(y), ldy);
-  else
-    hipLaunchKernelGGL((k_axpby<uint16_t>), grid, dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(x1), ld1, a, static_cast<const uint16_t*>(x2),
-                       ld2, b, n, d, static_cast<uint16_t*>(y), ldy);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return launch(k_axpby<decltype(t)>, dim3(ew_grid(n * (d / 4))), st, x1, ld1, a, x2, ld2, b, n, d, y, ldy);
+  });
 }
 
 extern "C" int sgf_gather_rows(const void* src, int64_t lds, int32_t src_dtype, int64_t n_src, const void* idx,
@@ -1800,19 +1687,10 @@ extern "C" int sgf_gather_rows(const void* src, int64_t lds, int32_t src_dtype, 
                   reinterpret_cast<uintptr_t>(dst) % (4 * ed) == 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(ew_grid(vec ? n_out * (d / 4) : n_out * d));
-#define SGF_GATHER(TS_, TD_, TI_)                                                                            \
-  hipLaunchKernelGGL((k_gather_rows<TS_, TD_, TI_>), grid, dim3(kThreads), 0, st, static_cast<const TS_*>(src), \
-                     lds, static_cast<const TI_*>(idx), n_out, d, n_src, static_cast<TD_*>(dst), ldd, vec)
-#define SGF_GATHER_I(TS_, TD_) \
-  do { if (idx_is_int64) SGF_GATHER(TS_, TD_, int64_t); else SGF_GATHER(TS_, TD_, int32_t); } while (0)
-  if (src_dtype == SGF_F32 && dst_dtype == SGF_F32) SGF_GATHER_I(float, float);
-  else if (src_dtype == SGF_F32) SGF_GATHER_I(float, uint16_t);
-  else if (dst_dtype == SGF_F32) SGF_GATHER_I(uint16_t, float);
-  else SGF_GATHER_I(uint16_t, uint16_t);
-#undef SGF_GATHER_I
-#undef SGF_GATHER
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_copy_types(src_dtype, dst_dtype, idx_is_int64, [&](auto ts, auto td, auto ti) {
+    return launch(k_gather_rows<decltype(ts), decltype(td), decltype(ti)>, grid, st, src, lds, idx, n_out, d, n_src, dst, ldd,
+                  vec);
+  });
 }
 
 // dst[i, :d] = src[idx ? idx[i] : i, :d] (storage change allowed), dst[i, d:d_pad] = 0 — the module-entry copy of node
@@ -1852,19 +1730,10 @@ extern "C" int sgf_pad_rows(const void* src, int64_t lds, int32_t src_dtype, int
   SGF_REQUIRE(src && dst && lds >= d && ldd >= d_pad, SGF_E_INVALID, "sgf_pad_rows: bad pointer / ld");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(ew_grid(n_out * d_pad));
-#define SGF_PAD(TS_, TD_, TI_)                                                                                      \
-  hipLaunchKernelGGL((k_pad_rows<TS_, TD_, TI_>), grid, dim3(kThreads), 0, st, static_cast<const TS_*>(src), lds, \
-                     static_cast<const TI_*>(idx), n_src, n_out, d, d_pad, static_cast<TD_*>(dst), ldd)
-#define SGF_PAD_I(TS_, TD_) \
-  do { if (idx && idx_is_int64) SGF_PAD(TS_, TD_, int64_t); else SGF_PAD(TS_, TD_, int32_t); } while (0)
-  if (src_dtype == SGF_F32 && dst_dtype == SGF_F32) SGF_PAD_I(float, float);
-  else if (src_dtype == SGF_F32) SGF_PAD_I(float, uint16_t);
-  else if (dst_dtype == SGF_F32) SGF_PAD_I(uint16_t, float);
-  else SGF_PAD_I(uint16_t, uint16_t);
-#undef SGF_PAD_I
-#undef SGF_PAD
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_copy_types(src_dtype, dst_dtype, idx && idx_is_int64, [&](auto ts, auto td, auto ti) {
+    return launch(k_pad_rows<decltype(ts), decltype(td), decltype(ti)>, grid, st, src, lds, idx, n_src, n_out, d, d_pad, dst,
+                  ldd);
+  });
 }
 
 extern "C" int sgf_sum_n(const void* const* xs, const int64_t* lds, int32_t k, int64_t n, int32_t d,
@@ -1886,24 +1755,14 @@ extern "C" int sgf_sum_n(const void* const* xs, const int64_t* lds, int32_t k, i
   for (int j = 0; j < k && wide; ++j) wide = lds[j] % 8 == 0 && reinterpret_cast<uintptr_t>(xs[j]) % 16 == 0;
   if (wide) {
     const dim3 grid8(ew_grid(n * (d / 8)));
-    uint16_t* y16 = static_cast<uint16_t*>(y);
     switch (k) {
-#define SGF_SUM_CASE(K_) case K_: hipLaunchKernelGGL((k_sum_n_bf16x8<K_>), grid8, dim3(kThreads), 0, st, a, n, d, y16, ldy); break;
+#define SGF_SUM_CASE(K_) case K_: return launch(k_sum_n_bf16x8<K_>, grid8, st, a, n, d, y, ldy);
       SGF_SUM_CASE(1) SGF_SUM_CASE(2) SGF_SUM_CASE(3) SGF_SUM_CASE(4) SGF_SUM_CASE(5) SGF_SUM_CASE(6) SGF_SUM_CASE(7)
       SGF_SUM_CASE(8)
 #undef SGF_SUM_CASE
     }
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
   }
-  const dim3 grid(ew_grid(n * (d / 4)));
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_sum_n<float>), grid, dim3(kThreads), 0, st, a, n, d, static_cast<float*>(y), ldy);
-  else
-    hipLaunchKernelGGL((k_sum_n<uint16_t>), grid, dim3(kThreads), 0, st, a, n, d,
-                       static_cast<uint16_t*>(y), ldy);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_dtype(dtype, [&](auto t) { return launch(k_sum_n<decltype(t)>, dim3(ew_grid(n * (d / 4))), st, a, n, d, y, ldy); });
 }
 
 // sgf_dropout and sgf_dropout_dev: `seed` is the seed itself, or (kDevSeed) the device address it is read from
@@ -1920,16 +1779,10 @@ static int dropout_launch(const char* who, const void* x, int64_t ldx, const voi
               "%s: seed_slot must be a non-null, 8-byte aligned device address", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
-  const dim3 grid(ew_grid(n * (d / 4)));
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_dropout<float, kDevSeed>), grid, dim3(kThreads), 0, st, static_cast<const float*>(x), ldx,
-                       static_cast<const float*>(res), ldr, p, scale, seed, n, d, static_cast<float*>(y), ldy);
-  else
-    hipLaunchKernelGGL((k_dropout<uint16_t, kDevSeed>), grid, dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(x), ldx, static_cast<const uint16_t*>(res), ldr, p, scale, seed,
-                       n, d, static_cast<uint16_t*>(y), ldy);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return launch(k_dropout<decltype(t), kDevSeed>, dim3(ew_grid(n * (d / 4))), st, x, ldx, res, ldr, p, scale, seed, n, d, y,
+                  ldy);
+  });
 }
 
 extern "C" int sgf_dropout(const void* x, int64_t ldx, const void* res, int64_t ldr, float p,
@@ -1958,31 +1811,16 @@ extern "C" int sgf_nll_fwd(const void* logits, int64_t ldl, int64_t n, int32_t c
   SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "sgf_nll_fwd: unknown dtype");
   SGF_REQUIRE(loss_sum, SGF_E_INVALID, "sgf_nll_fwd: null loss_sum");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (m == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(loss_sum, 0, sizeof(float), st));
-    return SGF_OK;
-  }
+  if (m == 0) return zero_floats(loss_sum, 1, st);
   SGF_REQUIRE(logits && labels && idx, SGF_E_INVALID, "sgf_nll_fwd: null pointer");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_nll_workspace_bytes(m), SGF_E_WORKSPACE,
               "sgf_nll_fwd: workspace too small");
-  int64_t b = (m + 63) / 64;
-  if (b > kNllMaxBlocks) b = kNllMaxBlocks;
-  const int nblk = static_cast<int>(b);
+  const int nblk = clamp_grid(ceil_div(m, 64), kNllMaxBlocks);
   float* part = static_cast<float*>(workspace);
-  if (c <= 64) {
-    if (dtype == SGF_F32)
-      hipLaunchKernelGGL((k_nll_fwd16<float>), dim3(nblk), dim3(kThreads), 0, st,
-                         static_cast<const float*>(logits), ldl, c, labels, idx, m, part);
-    else
-      hipLaunchKernelGGL((k_nll_fwd16<uint16_t>), dim3(nblk), dim3(kThreads), 0, st,
-                         static_cast<const uint16_t*>(logits), ldl, c, labels, idx, m, part);
-  } else if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_nll_fwd<float>), dim3(nblk), dim3(kThreads), 0, st,
-                       static_cast<const float*>(logits), ldl, c, labels, idx, m, part);
-  else
-    hipLaunchKernelGGL((k_nll_fwd<uint16_t>), dim3(nblk), dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(logits), ldl, c, labels, idx, m, part);
-  SGF_LAUNCH_CHECK();
+  int rc = c <= 64   // one wave per 4 rows, or per row
+               ? by_dtype(dtype, [&](auto t) { return launch(k_nll_fwd16<decltype(t)>, dim3(nblk), st, logits, ldl, c, labels, idx, m, part); })
+               : by_dtype(dtype, [&](auto t) { return launch(k_nll_fwd<decltype(t)>, dim3(nblk), st, logits, ldl, c, labels, idx, m, part); });
+  if (rc != SGF_OK) return rc;
   hipLaunchKernelGGL(k_nll_sum, dim3(1), dim3(64), 0, st, part, nblk, loss_sum);
   SGF_LAUNCH_CHECK();
   return SGF_OK;
@@ -2001,30 +1839,14 @@ extern "C" int sgf_nll_bwd(const void* logits, int64_t ldl, int64_t n, int32_t c
                                  static_cast<size_t>(n), st));
   if (m == 0) return SGF_OK;
   SGF_REQUIRE(logits && labels && idx, SGF_E_INVALID, "sgf_nll_bwd: null pointer");
-  int64_t b = (m + 3) / 4;
-  const int64_t cap = static_cast<int64_t>(kNumCU) * 8;
-  if (b > cap) b = cap;
-  if (c <= 64) {
-    int64_t b16 = (m + 15) / 16;
-    if (b16 > cap) b16 = cap;
-    if (dtype == SGF_F32)
-      hipLaunchKernelGGL((k_nll_bwd16<float>), dim3(static_cast<unsigned>(b16)), dim3(kThreads), 0, st,
-                         static_cast<const float*>(logits), ldl, c, labels, idx, m, gout, inv_denom,
-                         static_cast<float*>(dlogits), ldd);
-    else
-      hipLaunchKernelGGL((k_nll_bwd16<uint16_t>), dim3(static_cast<unsigned>(b16)), dim3(kThreads), 0, st,
-                         static_cast<const uint16_t*>(logits), ldl, c, labels, idx, m, gout, inv_denom,
-                         static_cast<uint16_t*>(dlogits), ldd);
-  } else if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_nll_bwd<float>), dim3(static_cast<unsigned>(b)), dim3(kThreads), 0, st,
-                       static_cast<const float*>(logits), ldl, c, labels, idx, m, gout, inv_denom,
-                       static_cast<float*>(dlogits), ldd);
-  else
-    hipLaunchKernelGGL((k_nll_bwd<uint16_t>), dim3(static_cast<unsigned>(b)), dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(logits), ldl, c, labels, idx, m, gout, inv_denom,
-                       static_cast<uint16_t*>(dlogits), ldd);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  const dim3 grid(clamp_grid(ceil_div(m, c <= 64 ? 16 : 4)));     // rows per block of the two kernels
+  if (c <= 64)
+    return by_dtype(dtype, [&](auto t) {
+      return launch(k_nll_bwd16<decltype(t)>, grid, st, logits, ldl, c, labels, idx, m, gout, inv_denom, dlogits, ldd);
+    });
+  return by_dtype(dtype, [&](auto t) {
+    return launch(k_nll_bwd<decltype(t)>, grid, st, logits, ldl, c, labels, idx, m, gout, inv_denom, dlogits, ldd);
+  });
 }
 
 extern "C" size_t sgf_colsum_workspace_bytes(int64_t n, int32_t d) {
@@ -2040,23 +1862,10 @@ extern "C" int sgf_colsum(const void* x, int64_t ldx, int64_t n, int32_t d, int3
   SGF_REQUIRE(dtype == SGF_F32 || dtype == SGF_BF16, SGF_E_INVALID, "sgf_colsum: unknown dtype");
   SGF_REQUIRE(out, SGF_E_INVALID, "sgf_colsum: null out");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    SGF_CHECK_HIP(hipMemsetAsync(out, 0, d * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_floats(out, d, st);
   SGF_REQUIRE(x && workspace && workspace_bytes >= sgf_colsum_workspace_bytes(n, d), SGF_E_WORKSPACE,
               "sgf_colsum: null x or workspace too small");
   const int nblk = stat_blocks(n);
-  float* part = static_cast<float*>(workspace);
-  if (dtype == SGF_F32)
-    hipLaunchKernelGGL((k_colsum_any<float>), dim3(nblk), dim3(kThreads), 0, st,
-                       static_cast<const float*>(x), ldx, n, d, part);
-  else
-    hipLaunchKernelGGL((k_colsum_any<uint16_t>), dim3(nblk), dim3(kThreads), 0, st,
-                       static_cast<const uint16_t*>(x), ldx, n, d, part);
-  SGF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sum_partials, dim3((d + 7) / 8), dim3(256), 0, st, part, nblk, d, out,
-                     static_cast<float*>(nullptr), d);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  int rc = by_dtype(dtype, [&](auto t) { return launch(k_colsum_any<decltype(t)>, dim3(nblk), st, x, ldx, n, d, workspace); });
+  return rc != SGF_OK ? rc : sum_partials(static_cast<float*>(workspace), nblk, d, out, nullptr, d, st);
 }

@@ -1461,6 +1461,7 @@ __global__ __launch_bounds__(256) void k_rowgemm_stats(const float* __restrict__
   if (g == 0 && c < len) stats[c] = (red[threadIdx.x] + red[64 + threadIdx.x]) + (red[128 + threadIdx.x] + red[192 + threadIdx.x]);
 }
 
+// ---- host side: every entry is checks, an argument struct, one launch call and (with statistics) one finalize ----------------
 int grid_blocks(int64_t n) {
   const int64_t tiles = (n + 31) / 32;
   int64_t b = (tiles + kRgWaves - 1) / kRgWaves;
@@ -1499,36 +1500,81 @@ int cat_vblocks(int64_t n, int d) {
   return vblocks;
 }
 
-template <bool STATS, int IO>
-int launch_rowgemm(const RowGemmArgs& a, int d, int blocks, hipStream_t st) {
+inline const uint16_t* bf(const void* p) { return static_cast<const uint16_t*>(p); }
+inline uint16_t* bf(void* p) { return static_cast<uint16_t*>(p); }
+inline const float* fl(const void* p) { return static_cast<const float*>(p); }
+inline float* fl(void* p) { return static_cast<float*>(p); }
+
+// the widths of the bf16 row kernels; f gets the width as a std::integral_constant
+inline bool bf16_rows(int d, int dtype) { return dtype == SGF_BF16 && (d == 64 || d == 128 || d == 256); }
+template <typename F>
+int by_width(const char* fn, int d, F&& f) {
   switch (d) {
-    case 64: hipLaunchKernelGGL((k_rowgemm_bf16<64, STATS, IO>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((k_rowgemm_bf16<128, STATS, IO>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-    case 256: {
-#ifdef SGF_PROBES   // timing ablations (make PROBES=1): SGF_ROWGEMM_DEBUG; not compiled into the release library
-      static EnvInt dbg_env{"SGF_ROWGEMM_DEBUG", 0};
-      const int dbg = dbg_env.get();
-      switch (IO == 0 && !STATS ? dbg : 0) {
-#define SGF_RG_DBG(X) case X: hipLaunchKernelGGL((k_rowgemm_bf16<256, false, 0, X>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-        SGF_RG_DBG(2) SGF_RG_DBG(4) SGF_RG_DBG(6)
-#undef SGF_RG_DBG
-        default: hipLaunchKernelGGL((k_rowgemm_bf16<256, STATS, IO>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-      }
-#else
-      hipLaunchKernelGGL((k_rowgemm_bf16<256, STATS, IO>), dim3(blocks), dim3(kRgThreads), 0, st, a);
-#endif
-      break;
-    }
-    default: set_error("sgf_gcn_epilogue: width %d not in {64, 128, 256}", d); return SGF_E_UNSUPPORTED;
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 256: return f(std::integral_constant<int, 256>{});
   }
+  set_error("%s: width %d not in {64, 128, 256}", fn, d);
+  return SGF_E_UNSUPPORTED;
+}
+
+template <typename Args>
+int launch(void (*kernel)(Args), int blocks, const Args& a, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRgThreads), 0, st, a);
   SGF_LAUNCH_CHECK();
   return SGF_OK;
 }
 
+template <bool STATS, int IO>
+int launch_rowgemm(const char* fn, const RowGemmArgs& a, int d, int blocks, hipStream_t st) {
+  return by_width(fn, d, [&](auto w) {
+    constexpr int D = decltype(w)::value;
+#ifdef SGF_PROBES   // timing ablations (make PROBES=1): SGF_ROWGEMM_DEBUG; not compiled into the release library
+    if constexpr (D == 256 && IO == 0 && !STATS) {
+      static EnvInt dbg_env{"SGF_ROWGEMM_DEBUG", 0};
+      switch (dbg_env.get()) {
+        case 2: return launch(k_rowgemm_bf16<256, false, 0, 2>, blocks, a, st);
+        case 4: return launch(k_rowgemm_bf16<256, false, 0, 4>, blocks, a, st);
+        case 6: return launch(k_rowgemm_bf16<256, false, 0, 6>, blocks, a, st);
+      }
+    }
+#endif
+    return launch(k_rowgemm_bf16<D, STATS, IO>, blocks, a, st);
+  });
+}
+
 bool supported(int32_t d_in, int32_t d_out, int32_t dtype) {
   if (f32_storage(dtype)) return linear_f32_supported(d_in, d_out);   // fp32 storage: csrc/linear_f32.hip, linear_f32x.hip
-  return dtype == SGF_BF16 && d_in == d_out && (d_in == 64 || d_in == 128 || d_in == 256);
+  return d_in == d_out && bf16_rows(d_in, dtype);
 }
+
+// bf16 row operands: p null only where optional, at least `width` columns, rows on 16-byte boundaries
+struct RowOp {
+  const void* p;
+  int64_t ld;
+  int width;
+  bool optional = false;
+};
+bool rows16(const void* p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 8 == 0; }
+template <size_t K>
+bool rows_given(const RowOp (&ops)[K]) {
+  for (const RowOp& o : ops)
+    if (!o.p && !o.optional) return false;
+  return true;
+}
+template <size_t K>
+int rows_fit(const char* fn, const RowOp (&ops)[K]) {
+  for (const RowOp& o : ops)
+    SGF_REQUIRE(!o.p || o.ld >= o.width, SGF_E_INVALID, "%s: leading dimension smaller than the width", fn);
+  for (const RowOp& o : ops)
+    SGF_REQUIRE(!o.p || rows16(o.p, o.ld), SGF_E_INVALID,
+                "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 8 elements)", fn);
+  return SGF_OK;
+}
+inline bool fits_u32_bytes(int64_t n, int64_t ld) {   // bf16 rows addressed with 32-bit byte offsets
+  return static_cast<uint64_t>(n) * static_cast<uint64_t>(ld) * 2 < 0xffffff00ull;
+}
+inline size_t tile_bytes(int64_t n, int d) { return static_cast<size_t>((n + 31) / 32) * 32 * static_cast<size_t>(d) * 2; }
 
 int check_common(const char* who, const void* a, int64_t lda, const void* w, int64_t ldw, int64_t n, int32_t d_in,
                  int32_t d_out, int32_t dtype, const void* y, int64_t ldy) {
@@ -1544,63 +1590,53 @@ int check_common(const char* who, const void* a, int64_t lda, const void* w, int
                 SGF_E_INVALID, "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 4 elements)", who);
     return SGF_OK;
   }
-  SGF_REQUIRE(lda >= d_in && ldy >= d_out && ldw >= (d_in > d_out ? d_in : d_out), SGF_E_INVALID,
-              "%s: leading dimension smaller than the width", who);
-  SGF_REQUIRE(lda % 8 == 0 && ldy % 8 == 0 && ldw % 8 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(w) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0,
-              SGF_E_INVALID, "%s: rows must be 16-byte aligned (pointers % 16, leading dims % 8 elements)", who);
+  const RowOp rows[] = {{a, lda, d_in}, {y, ldy, d_out}, {w, ldw, d_in > d_out ? d_in : d_out}};
+  return rows_fit(who, rows);
+}
+
+// the three bf16-only entries: sizes and storage
+int check_bf16_rows(const char* fn, int64_t n, int d, int dtype) {
+  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "%s: negative n", fn);
+  SGF_REQUIRE(bf16_rows(d, dtype), SGF_E_UNSUPPORTED, "%s: bf16 storage, d in {64, 128, 256} (got d = %d, dtype %d)", fn, d,
+              dtype);
   return SGF_OK;
 }
 
 template <int MODE>
-int launch_hrow(const HRowArgs& a, int d, hipStream_t st) {
-  const int blocks = grid_blocks(a.n);
-  switch (d) {
-    case 64: hipLaunchKernelGGL((k_hrow_bf16<64, MODE>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((k_hrow_bf16<128, MODE>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-    case 256: hipLaunchKernelGGL((k_hrow_bf16<256, MODE>), dim3(blocks), dim3(kRgThreads), 0, st, a); break;
-    default: set_error("hrow: width %d not in {64, 128, 256}", d); return SGF_E_UNSUPPORTED;
-  }
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+int launch_hrow(const char* fn, const HRowArgs& a, int d, hipStream_t st) {
+  return by_width(fn, d, [&](auto w) { return launch(k_hrow_bf16<decltype(w)::value, MODE>, grid_blocks(a.n), a, st); });
 }
-
-bool rows16(const void* p, int64_t ld) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 8 == 0; }
 
 }  // namespace
 
 // ---- internal entry points used by attn.hip (declared in common.h) ----
 bool hrow_supported(int d, int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, const void* c, int64_t ldc,
                     const void* o, int64_t ldo) {
-  return dtype == SGF_BF16 && (d == 64 || d == 128 || d == 256) && rows16(a, lda) && (!b || rows16(b, ldb)) &&
-         (!c || rows16(c, ldc)) && rows16(o, ldo);
+  return bf16_rows(d, dtype) && rows16(a, lda) && (!b || rows16(b, ldb)) && (!c || rows16(c, ldc)) && rows16(o, ldo);
 }
 
-size_t hrow_partial_bytes(int64_t n, int d) { return static_cast<size_t>((n + 31) / 32) * 32 * static_cast<size_t>(d) * 2; }
+size_t hrow_partial_bytes(int64_t n, int d) { return tile_bytes(n, d); }
 
 int hrow_fwd(const void* h, int64_t ldh, int64_t n, int d, const float* M, const float* m, const float* w,
              const float* beta, void* out, int64_t ldo, float* den, hipStream_t st) {
-  HRowArgs a{static_cast<const uint16_t*>(h), ldh, nullptr, 0, M, 0, m, w, beta, den, static_cast<uint16_t*>(out), ldo,
-             nullptr, n, nullptr, nullptr, 0};
-  return launch_hrow<kHF>(a, d, st);
+  HRowArgs a{bf(h), ldh, nullptr, 0, M, 0, m, w, beta, den, bf(out), ldo, nullptr, n, nullptr, nullptr, 0};
+  return launch_hrow<kHF>("hrow_fwd", a, d, st);
 }
 
 // part = (g M^T) / den - ((g.o) / den) w;  rowscal (optional) = (1 / den, -(g.o) / den) per row
 int hrow_bwd_pre(const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den, int64_t n, int d,
                  const float* M, const float* w, void* partial, float* rowscal, hipStream_t st) {
-  HRowArgs a{static_cast<const uint16_t*>(g), ldg, static_cast<const uint16_t*>(o), ldo, M, 1, w, nullptr, nullptr,
-             const_cast<float*>(den), nullptr, 0, static_cast<uint4*>(partial), n, reinterpret_cast<float2*>(rowscal),
-             nullptr, 0};
-  return launch_hrow<kHB1>(a, d, st);
+  HRowArgs a{bf(g), ldg, bf(o), ldo, M, 1, w, nullptr, nullptr, const_cast<float*>(den), nullptr, 0,
+             static_cast<uint4*>(partial), n, reinterpret_cast<float2*>(rowscal), nullptr, 0};
+  return launch_hrow<kHB1>("hrow_bwd_pre", a, d, st);
 }
 
 // dh = h D + ds + part
 int hrow_bwd_post(const void* h, int64_t ldh, int64_t n, int d, const float* Dm, const float* ds, const void* partial,
                   const void* addend, int64_t ldadd, void* dh, int64_t lddh, hipStream_t st) {
-  HRowArgs b{static_cast<const uint16_t*>(h), ldh, nullptr, 0, Dm, 0, ds, nullptr, nullptr, nullptr,
-             static_cast<uint16_t*>(dh), lddh, const_cast<uint4*>(static_cast<const uint4*>(partial)), n, nullptr,
-             static_cast<const uint16_t*>(addend), ldadd};
-  return launch_hrow<kHB2>(b, d, st);
+  HRowArgs b{bf(h), ldh, nullptr, 0, Dm, 0, ds, nullptr, nullptr, nullptr, bf(dh), lddh,
+             const_cast<uint4*>(static_cast<const uint4*>(partial)), n, nullptr, bf(addend), ldadd};
+  return launch_hrow<kHB2>("hrow_bwd_post", b, d, st);
 }
 
 int hrow_bwd(const void* h, int64_t ldh, const void* g, int64_t ldg, const void* o, int64_t ldo, const float* den,
@@ -1623,7 +1659,7 @@ extern "C" int32_t sgf_row_lap_rows(int32_t kind, int32_t d, int32_t dtype) {
     if (d <= 0 || d % 32 != 0 || d > 256) return -1;
     return static_cast<int32_t>(head_lap_rows(kind == 7, cap_n));
   }
-  if (d != 64 && d != 128 && d != 256) return -1;
+  if (!bf16_rows(d, dtype)) return -1;
   int vblocks;
   switch (kind) {
     case 0: case 5: vblocks = grid_blocks(cap_n); break;
@@ -1647,60 +1683,76 @@ extern "C" size_t sgf_gcn_epilogue_workspace_bytes(int64_t n, int32_t d_out) {
   return static_cast<size_t>(b) * 2 * static_cast<size_t>(d_out) * sizeof(float);
 }
 
+// ---- BatchNorm's shifted column sums: per-block partials in the workspace, summed in fixed order by one more launch ----------
+namespace {
+
+// no rows: the sums are zero
+int zero_stats(float* stats, int d_out, hipStream_t st) {
+  return stats ? zero_floats(stats, 2 * d_out, st) : SGF_OK;
+}
+
+// *spart = where the launch leaves its partials (null without stats: the kernel then computes none)
+int stats_partials(const char* fn, const float* stats, void* workspace, size_t bytes, int64_t n, int d_out, float** spart) {
+  *spart = nullptr;
+  if (!stats) return SGF_OK;
+  const size_t need = sgf_gcn_epilogue_workspace_bytes(n, d_out);
+  SGF_REQUIRE(workspace && bytes >= need, SGF_E_WORKSPACE, "%s: workspace %zu < %zu", fn, bytes, need);
+  *spart = static_cast<float*>(workspace);
+  return SGF_OK;
+}
+
+// rc: the status of the launch that wrote spart
+int finalize_stats(int rc, const float* spart, int nblk, int d_out, float* stats, hipStream_t st) {
+  if (rc != SGF_OK || !stats) return rc;
+  hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, spart, nblk, 2 * d_out, stats);
+  SGF_LAUNCH_CHECK();
+  return SGF_OK;
+}
+
+// fp32 storage of sgf_gcn_epilogue_stats (bias) and _stats_add (addend, [n, d_out]): csrc/linear_f32.hip, then the sums
+int linear_f32_stats(const void* a, int64_t lda, int64_t n, int d_in, int d_out, const void* w, int64_t ldw, const float* bias,
+                     const void* addend, const float* shift, void* y, int64_t ldy, float* spart, float* stats, int dtype,
+                     hipStream_t st) {
+  const int rc = linear_f32(fl(a), lda, n, d_in, d_out, fl(w), ldw, 1, bias, fl(addend), addend ? d_out : 0, shift, fl(y), ldy,
+                            spart, st, dtype == SGF_F32_BF16X3);
+  return finalize_stats(rc, spart, linear_f32_blocks(n), d_out, stats, st);
+}
+
+}  // namespace
+
 extern "C" int sgf_gcn_epilogue_stats(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
                                       int64_t n, int32_t d_in, int32_t d_out, int32_t dtype, void* y, int64_t ldy,
                                       const float* shift, float* stats, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  int rc = check_common("sgf_gcn_epilogue_stats", a, lda, w, ldw, n, d_in, d_out, dtype, y, ldy);
+  const char* fn = "sgf_gcn_epilogue_stats";
+  int rc = check_common(fn, a, lda, w, ldw, n, d_in, d_out, dtype, y, ldy);
   if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (stats) SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * static_cast<size_t>(d_out) * sizeof(float), st));
-    return SGF_OK;
-  }
-  if (f32_storage(dtype)) {
-    float* spart = nullptr;
-    if (stats) {
-      SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
-                  "sgf_gcn_epilogue_stats: workspace %zu < %zu", workspace_bytes, sgf_gcn_epilogue_workspace_bytes(n, d_out));
-      spart = static_cast<float*>(workspace);
-    }
-    rc = linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, bias, nullptr,
-                    0, shift, static_cast<float*>(y), ldy, spart, st, dtype == SGF_F32_BF16X3);
-    if (rc != SGF_OK || !stats) return rc;
-    hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, spart, linear_f32_blocks(n),
-                       2 * d_out, stats);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
-  }
-  const int blocks = grid_blocks(n);
-  RowGemmArgs args{static_cast<const uint16_t*>(a), lda, static_cast<const uint16_t*>(w), ldw, 0, bias, shift,
-                   nullptr, static_cast<uint16_t*>(y), ldy, n, nullptr};
-  if (!stats) return launch_rowgemm<false, 0>(args, d_out, blocks, st);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
-              "sgf_gcn_epilogue_stats: workspace %zu < %zu", workspace_bytes, sgf_gcn_epilogue_workspace_bytes(n, d_out));
-  args.spart = static_cast<float*>(workspace);
-  rc = launch_rowgemm<true, 0>(args, d_out, blocks, st);
+  if (n == 0) return zero_stats(stats, d_out, st);
+  float* spart;
+  rc = stats_partials(fn, stats, workspace, workspace_bytes, n, d_out, &spart);
   if (rc != SGF_OK) return rc;
-  hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, args.spart, blocks, 2 * d_out,
-                     stats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  if (f32_storage(dtype))
+    return linear_f32_stats(a, lda, n, d_in, d_out, w, ldw, bias, nullptr, shift, y, ldy, spart, stats, dtype, st);
+  const int blocks = grid_blocks(n);
+  RowGemmArgs args{bf(a), lda, bf(w), ldw, 0, bias, shift, spart, bf(y), ldy, n, nullptr};
+  rc = !stats ? launch_rowgemm<false, 0>(fn, args, d_out, blocks, st) : launch_rowgemm<true, 0>(fn, args, d_out, blocks, st);
+  return finalize_stats(rc, spart, blocks, d_out, stats, st);
 }
 
 extern "C" int sgf_gcn_epilogue_dx(const void* dy, int64_t lddy, const void* w, int64_t ldw, int64_t n, int32_t d_in,
                                    int32_t d_out, int32_t dtype, void* dx, int64_t lddx, void* stream) {
   // dx [n, d_in] = dy [n, d_out] W [d_out, d_in]: contraction over W's rows
-  int rc = check_common("sgf_gcn_epilogue_dx", dy, lddy, w, ldw, n, d_out, d_in, dtype, dx, lddx);
+  const char* fn = "sgf_gcn_epilogue_dx";
+  int rc = check_common(fn, dy, lddy, w, ldw, n, d_out, d_in, dtype, dx, lddx);
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (f32_storage(dtype))
-    return linear_f32(static_cast<const float*>(dy), lddy, n, d_out, d_in, static_cast<const float*>(w), ldw, 0, nullptr,
-                      nullptr, 0, nullptr, static_cast<float*>(dx), lddx, nullptr, static_cast<hipStream_t>(stream),
+    return linear_f32(fl(dy), lddy, n, d_out, d_in, fl(w), ldw, 0, nullptr, nullptr, 0, nullptr, fl(dx), lddx, nullptr, st,
                       dtype == SGF_F32_BF16X3);
-  RowGemmArgs args{static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(w), ldw, 1, nullptr, nullptr,
-                   nullptr, static_cast<uint16_t*>(dx), lddx, n, nullptr};
-  return launch_rowgemm<false, 0>(args, d_in, grid_blocks(n), static_cast<hipStream_t>(stream));
+  RowGemmArgs args{bf(dy), lddy, bf(w), ldw, 1, nullptr, nullptr, nullptr, bf(dx), lddx, n, nullptr};
+  return launch_rowgemm<false, 0>(fn, args, d_in, grid_blocks(n), st);
 }
 
 // Both input gradients of the two-operand Linear from ONE read of dy out of HBM:  dx1 = dy W[:, :d], dx2 = dy W[:, d:]
@@ -1710,63 +1762,48 @@ extern "C" int sgf_gcn_epilogue_dx(const void* dy, int64_t lddy, const void* w, 
 extern "C" int sgf_gcn_epilogue_dx2(const void* dy, int64_t lddy, const void* w1, const void* w2, int64_t ldw, int64_t n,
                                     int32_t d, int32_t dtype, void* dx1, int64_t lddx1, void* dx2, int64_t lddx2,
                                     int32_t pair, void* stream) {
-  int rc = check_common("sgf_gcn_epilogue_dx2", dy, lddy, w1, ldw, n, d, d, dtype, dx1, lddx1);
+  const char* fn = "sgf_gcn_epilogue_dx2";
+  int rc = check_common(fn, dy, lddy, w1, ldw, n, d, d, dtype, dx1, lddx1);
   if (rc != SGF_OK) return rc;
-  rc = check_common("sgf_gcn_epilogue_dx2", dy, lddy, w2, ldw, n, d, d, dtype, dx2, lddx2);
+  rc = check_common(fn, dy, lddy, w2, ldw, n, d, d, dtype, dx2, lddx2);
   if (rc != SGF_OK) return rc;
   if (n == 0) return SGF_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const int pairs = dx2_pair_vblocks(n);
   if (f32_storage(dtype) || !pair || pairs == 0) {
     rc = sgf_gcn_epilogue_dx(dy, lddy, w1, ldw, n, d, d, dtype, dx1, lddx1, stream);
     if (rc != SGF_OK) return rc;
     return sgf_gcn_epilogue_dx(dy, lddy, w2, ldw, n, d, d, dtype, dx2, lddx2, stream);
   }
-  RowGemmArgs args{static_cast<const uint16_t*>(dy), lddy, static_cast<const uint16_t*>(w1), ldw, 1, nullptr, nullptr,
-                   nullptr, static_cast<uint16_t*>(dx1), lddx1, n, nullptr,
-                   static_cast<const uint16_t*>(w2), static_cast<uint16_t*>(dx2), lddx2, 1};
-  return launch_rowgemm<false, 0>(args, d, 2 * pairs, st);
+  RowGemmArgs args{bf(dy), lddy, bf(w1), ldw, 1, nullptr, nullptr, nullptr, bf(dx1), lddx1, n, nullptr,
+                   bf(w2), bf(dx2), lddx2, 1};
+  return launch_rowgemm<false, 0>(fn, args, d, 2 * pairs, static_cast<hipStream_t>(stream));
 }
 
 // dy = dz W[:, :d], acc_out = dz W[:, d:] + gadd + acc_in (gadd / acc_in nullable): see k_dx2acc_bf16
-extern "C" int32_t sgf_gcn_epilogue_dx2_acc_supported(int32_t d, int32_t dtype) {
-  return dtype == SGF_BF16 && (d == 64 || d == 128 || d == 256) ? 1 : 0;
-}
+extern "C" int32_t sgf_gcn_epilogue_dx2_acc_supported(int32_t d, int32_t dtype) { return bf16_rows(d, dtype) ? 1 : 0; }
 
 extern "C" int sgf_gcn_epilogue_dx2_acc(const void* dz, int64_t lddz, const void* w, int64_t ldw, int64_t n, int32_t d,
                                         int32_t dtype, void* dy, int64_t lddy, const void* gadd, int64_t ldg,
                                         const void* acc_in, int64_t ldai, void* acc_out, int64_t ldao, void* stream) {
   const char* fn = "sgf_gcn_epilogue_dx2_acc";
-  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "%s: negative n", fn);
-  SGF_REQUIRE(sgf_gcn_epilogue_dx2_acc_supported(d, dtype), SGF_E_UNSUPPORTED,
-              "%s: bf16 storage, d in {64, 128, 256} (got d = %d, dtype %d)", fn, d, dtype);
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(dz && w && dy && acc_out, SGF_E_INVALID, "%s: null pointer", fn);
-  SGF_REQUIRE(lddz >= d && lddy >= d && ldao >= d && ldw >= 2 * d && (!gadd || ldg >= d) && (!acc_in || ldai >= d),
-              SGF_E_INVALID, "%s: leading dimension smaller than the width", fn);
-  SGF_REQUIRE(rows16(dz, lddz) && rows16(w, ldw) && rows16(dy, lddy) && rows16(acc_out, ldao) &&
-                  (!gadd || rows16(gadd, ldg)) && (!acc_in || rows16(acc_in, ldai)),
-              SGF_E_INVALID, "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 8 elements)", fn);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Dx2AccArgs a{static_cast<const uint16_t*>(dz), lddz, static_cast<const uint16_t*>(w), ldw, static_cast<uint16_t*>(dy), lddy,
-               static_cast<const uint16_t*>(gadd), ldg, static_cast<const uint16_t*>(acc_in), ldai,
-               static_cast<uint16_t*>(acc_out), ldao, n};
+  int rc = check_bf16_rows(fn, n, d, dtype);
+  if (rc != SGF_OK || n == 0) return rc;
+  const RowOp rows[] = {{dz, lddz, d}, {dy, lddy, d}, {acc_out, ldao, d}, {w, ldw, 2 * d}, {gadd, ldg, d, true},
+                        {acc_in, ldai, d, true}};
+  SGF_REQUIRE(rows_given(rows), SGF_E_INVALID, "%s: null pointer", fn);
+  rc = rows_fit(fn, rows);
+  if (rc != SGF_OK) return rc;
+  Dx2AccArgs a{bf(dz), lddz, bf(w), ldw, bf(dy), lddy, bf(gadd), ldg, bf(acc_in), ldai, bf(acc_out), ldao, n};
   const int vblocks = dx2_acc_vblocks(n, d);
-  if (d == 256) {
-    hipLaunchKernelGGL((k_dx2acc_bf16<256, 2>), dim3(2 * vblocks), dim3(kRgThreads), 0, st, a);
-  } else if (d == 128) {
-    hipLaunchKernelGGL((k_dx2acc_bf16<128, 1>), dim3(vblocks), dim3(kRgThreads), 0, st, a);
-  } else {
-    hipLaunchKernelGGL((k_dx2acc_bf16<64, 1>), dim3(vblocks), dim3(kRgThreads), 0, st, a);
-  }
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // not by_width: the code object holds these kernels widest first, in the order the host names them
+  if (d == 256) return launch(k_dx2acc_bf16<256, 2>, 2 * vblocks, a, st);
+  if (d == 128) return launch(k_dx2acc_bf16<128, 1>, vblocks, a, st);
+  return launch(k_dx2acc_bf16<64, 1>, vblocks, a, st);
 }
 
 // ---- backward of the GCN layer's dense half: BatchNorm backward + both input gradients, dx0 accumulated ------------------
-extern "C" int32_t sgf_gcn_bn_bwd_dx_supported(int32_t d, int32_t dtype) {
-  return dtype == SGF_BF16 && (d == 64 || d == 128 || d == 256) ? 1 : 0;
-}
+extern "C" int32_t sgf_gcn_bn_bwd_dx_supported(int32_t d, int32_t dtype) { return bf16_rows(d, dtype) ? 1 : 0; }
 
 extern "C" size_t sgf_gcn_bn_bwd_dx_workspace_bytes(int64_t n, int32_t d) {
   (void)n; (void)d;
@@ -1780,110 +1817,82 @@ extern "C" int sgf_gcn_bn_bwd_dx(const void* gy, int64_t ldg, const void* z, int
                                  void* acc_out, size_t acc_bytes, void* dx0, int64_t lddx0, int32_t add_gy, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   const char* fn = "sgf_gcn_bn_bwd_dx";
-  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "%s: negative n", fn);
-  SGF_REQUIRE(sgf_gcn_bn_bwd_dx_supported(d, dtype), SGF_E_UNSUPPORTED,
-              "%s: bf16 storage, d in {64, 128, 256} (got d = %d, dtype %d)", fn, d, dtype);
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(gy && z && mean && rstd && w && dz && dy && (!training || stats), SGF_E_INVALID, "%s: null pointer", fn);
+  int rc = check_bf16_rows(fn, n, d, dtype);
+  if (rc != SGF_OK || n == 0) return rc;
+  const RowOp rows[] = {{gy, ldg, d}, {z, ldz, d}, {dz, lddz, d}, {dy, lddy, d}, {w, ldw, 2 * d}, {dx0, lddx0, d, true}};
+  SGF_REQUIRE(rows_given(rows) && mean && rstd && (!training || stats), SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE((dx0 != nullptr) != (acc_out != nullptr), SGF_E_INVALID,
               "%s: exactly one of dx0 (row-major result) and acc_out (running sum) must be given", fn);
-  SGF_REQUIRE(ldg >= d && ldz >= d && lddz >= d && lddy >= d && ldw >= 2 * d && (!dx0 || lddx0 >= d), SGF_E_INVALID,
-              "%s: leading dimension smaller than the width", fn);
-  SGF_REQUIRE(rows16(gy, ldg) && rows16(z, ldz) && rows16(w, ldw) && rows16(dz, lddz) && rows16(dy, lddy) &&
-                  (!dx0 || rows16(dx0, lddx0)),
-              SGF_E_INVALID, "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 8 elements)", fn);
-  SGF_REQUIRE(static_cast<uint64_t>(n) * static_cast<uint64_t>(lddz) * 2 < 0xffffff00ull &&
-                  static_cast<uint64_t>(n) * static_cast<uint64_t>(ldg) * 2 < 0xffffff00ull &&
-                  static_cast<uint64_t>(n) * static_cast<uint64_t>(ldz) * 2 < 0xffffff00ull &&
-                  static_cast<uint64_t>(n) * static_cast<uint64_t>(lddy) * 2 < 0xffffff00ull &&
-                  (!dx0 || static_cast<uint64_t>(n) * static_cast<uint64_t>(lddx0) * 2 < 0xffffff00ull),
+  rc = rows_fit(fn, rows);
+  if (rc != SGF_OK) return rc;
+  SGF_REQUIRE(fits_u32_bytes(n, lddz) && fits_u32_bytes(n, ldg) && fits_u32_bytes(n, ldz) && fits_u32_bytes(n, lddy) &&
+                  (!dx0 || fits_u32_bytes(n, lddx0)),
               SGF_E_UNSUPPORTED, "%s: an operand beyond 4 GiB (32-bit offsets)", fn);
   const size_t need = sgf_gcn_epilogue_partial_bytes(n, d);
   SGF_REQUIRE((!acc_in && !acc_out) || acc_bytes >= need, SGF_E_WORKSPACE, "%s: running-sum buffer %zu < %zu", fn, acc_bytes, need);
   SGF_REQUIRE((!acc_in || reinterpret_cast<uintptr_t>(acc_in) % 16 == 0) && (!acc_out || reinterpret_cast<uintptr_t>(acc_out) % 16 == 0),
               SGF_E_INVALID, "%s: running-sum buffers must be 16-byte aligned", fn);
-  const int roles = d / 64;
   const int vblocks = bn_bwd_dx_vblocks(n, d);
-  BnBwdDxArgs a{static_cast<const uint16_t*>(gy), ldg, static_cast<const uint16_t*>(z), ldz, mean, rstd, gamma, beta,
-                stats, inv_n, training, relu, static_cast<const uint16_t*>(w), ldw, static_cast<uint16_t*>(dz), lddz,
-                static_cast<uint16_t*>(dy), lddy, static_cast<const uint4*>(acc_in), static_cast<uint4*>(acc_out),
-                static_cast<uint16_t*>(dx0), lddx0, add_gy, n, nullptr};
+  BnBwdDxArgs a{bf(gy), ldg, bf(z), ldz, mean, rstd, gamma, beta, stats, inv_n, training, relu, bf(w), ldw, bf(dz), lddz,
+                bf(dy), lddy, static_cast<const uint4*>(acc_in), static_cast<uint4*>(acc_out), bf(dx0), lddx0, add_gy, n,
+                nullptr};
   hipStream_t st = static_cast<hipStream_t>(stream);
   // the per-tile rendezvous of a group's blocks (optional: without a workspace, or under SGF_GCN_BWD_SYNC=0, they run free)
   static EnvInt sync_env{"SGF_GCN_BWD_SYNC", 1};
-  if (roles > 1 && workspace && workspace_bytes >= sgf_gcn_bn_bwd_dx_workspace_bytes(n, d) && sync_env.get() != 0 &&
+  if (d > 64 && workspace && workspace_bytes >= sgf_gcn_bn_bwd_dx_workspace_bytes(n, d) && sync_env.get() != 0 &&
       reinterpret_cast<uintptr_t>(workspace) % 4 == 0) {
     a.sync = static_cast<uint32_t*>(workspace);
     SGF_CHECK_HIP(hipMemsetAsync(workspace, 0, sgf_gcn_bn_bwd_dx_workspace_bytes(n, d), st));
   }
-  if (d == 64) hipLaunchKernelGGL((k_bn_bwd_dx_bf16<64, 1>), dim3(vblocks), dim3(kRgThreads), 0, st, a);
-  else if (d == 128) hipLaunchKernelGGL((k_bn_bwd_dx_bf16<128, 2>), dim3(vblocks * 2), dim3(kRgThreads), 0, st, a);
-  else {
+  return by_width(fn, d, [&](auto w_) {
+    constexpr int D = decltype(w_)::value, R = D / 64;
 #ifdef SGF_PROBES   // timing ablations (make PROBES=1): SGF_GCN_BWD_DEBUG; not compiled into the release library
-    static EnvInt dbg_env{"SGF_GCN_BWD_DEBUG", 0};
-    switch (dbg_env.get()) {
-#define SGF_BWD_DBG(X) case X: hipLaunchKernelGGL((k_bn_bwd_dx_bf16<256, 4, X>), dim3(vblocks * 4), dim3(kRgThreads), 0, st, a); break;
-      SGF_BWD_DBG(1) SGF_BWD_DBG(2) SGF_BWD_DBG(3) SGF_BWD_DBG(4) SGF_BWD_DBG(8) SGF_BWD_DBG(12) SGF_BWD_DBG(15)
+    if constexpr (D == 256) {
+      static EnvInt dbg_env{"SGF_GCN_BWD_DEBUG", 0};
+      switch (dbg_env.get()) {
+#define SGF_BWD_DBG(X) case X: return launch(k_bn_bwd_dx_bf16<256, 4, X>, vblocks * 4, a, st);
+        SGF_BWD_DBG(1) SGF_BWD_DBG(2) SGF_BWD_DBG(3) SGF_BWD_DBG(4) SGF_BWD_DBG(8) SGF_BWD_DBG(12) SGF_BWD_DBG(15)
 #undef SGF_BWD_DBG
-      default: hipLaunchKernelGGL((k_bn_bwd_dx_bf16<256, 4>), dim3(vblocks * 4), dim3(kRgThreads), 0, st, a); break;
+      }
     }
-#else
-    hipLaunchKernelGGL((k_bn_bwd_dx_bf16<256, 4>), dim3(vblocks * 4), dim3(kRgThreads), 0, st, a);
 #endif
-  }
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+    return launch(k_bn_bwd_dx_bf16<D, R>, vblocks * R, a, st);
+  });
 }
 
 // ---- the two-operand Linear in ONE pass (paired launch at d = 256) ---------------------------------------------------
-extern "C" int32_t sgf_gcn_epilogue_cat_supported(int32_t d, int32_t dtype) {
-  return dtype == SGF_BF16 && (d == 64 || d == 128 || d == 256) ? 1 : 0;
-}
+extern "C" int32_t sgf_gcn_epilogue_cat_supported(int32_t d, int32_t dtype) { return bf16_rows(d, dtype) ? 1 : 0; }
 
 extern "C" int sgf_gcn_epilogue_cat(const void* a1, int64_t lda1, const void* a2, int64_t lda2, const void* w, int64_t ldw,
                                     const float* bias, int64_t n, int32_t d, int32_t dtype, void* y, int64_t ldy,
                                     const float* shift, float* stats, void* workspace, size_t workspace_bytes,
                                     void* stream) {
   const char* fn = "sgf_gcn_epilogue_cat";
-  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "%s: negative n", fn);
-  SGF_REQUIRE(sgf_gcn_epilogue_cat_supported(d, dtype), SGF_E_UNSUPPORTED,
-              "%s: bf16 storage, d in {64, 128, 256} (got d = %d, dtype %d)", fn, d, dtype);
+  int rc = check_bf16_rows(fn, n, d, dtype);
+  if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (stats) SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * static_cast<size_t>(d) * sizeof(float), st));
-    return SGF_OK;
-  }
-  SGF_REQUIRE(a1 && a2 && w && y, SGF_E_INVALID, "%s: null pointer", fn);
-  SGF_REQUIRE(lda1 >= d && lda2 >= d && ldy >= d && ldw >= 2 * d, SGF_E_INVALID, "%s: leading dimension smaller than the width", fn);
-  SGF_REQUIRE(rows16(a1, lda1) && rows16(a2, lda2) && rows16(w, ldw) && rows16(y, ldy), SGF_E_INVALID,
-              "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% 8 elements)", fn);
-  const int vblocks = cat_vblocks(n, d);
-  RowGemm2Args args{static_cast<const uint16_t*>(a1), lda1, static_cast<const uint16_t*>(a2), lda2,
-                    static_cast<const uint16_t*>(w), ldw, bias, shift, nullptr, static_cast<uint16_t*>(y), ldy, n};
-  if (stats) {
-    SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d), SGF_E_WORKSPACE,
-                "%s: workspace %zu < %zu", fn, workspace_bytes, sgf_gcn_epilogue_workspace_bytes(n, d));
-    args.spart = static_cast<float*>(workspace);
-  }
-#define SGF_RG2(D_, R_)                                                                                                 \
-  if (stats) hipLaunchKernelGGL((k_rowgemm2_bf16<D_, R_, true>), dim3(vblocks * R_), dim3(kRgThreads), 0, st, args);     \
-  else hipLaunchKernelGGL((k_rowgemm2_bf16<D_, R_, false>), dim3(vblocks * R_), dim3(kRgThreads), 0, st, args)
-  if (d == 64) { SGF_RG2(64, 1); }
-  else if (d == 128) { SGF_RG2(128, 1); }
-  else { SGF_RG2(256, 2); }
-#undef SGF_RG2
-  SGF_LAUNCH_CHECK();
-  if (stats) {
-    hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d + 63) / 64), dim3(256), 0, st, args.spart, vblocks, 2 * d, stats);
-    SGF_LAUNCH_CHECK();
-  }
-  return SGF_OK;
+  if (n == 0) return zero_stats(stats, d, st);
+  const RowOp rows[] = {{a1, lda1, d}, {a2, lda2, d}, {y, ldy, d}, {w, ldw, 2 * d}};
+  SGF_REQUIRE(rows_given(rows), SGF_E_INVALID, "%s: null pointer", fn);
+  rc = rows_fit(fn, rows);
+  if (rc != SGF_OK) return rc;
+  float* spart;
+  rc = stats_partials(fn, stats, workspace, workspace_bytes, n, d, &spart);
+  if (rc != SGF_OK) return rc;
+  const int vblocks = cat_vblocks(n, d);                // the statistics have one partial row per VIRTUAL block
+  RowGemm2Args args{bf(a1), lda1, bf(a2), lda2, bf(w), ldw, bias, shift, spart, bf(y), ldy, n};
+  rc = by_width(fn, d, [&](auto w_) {
+    return by_flag(stats, [&](auto s) {
+      constexpr int D = decltype(w_)::value, R = D == 256 ? 2 : 1;
+      return launch(k_rowgemm2_bf16<D, R, decltype(s)::value>, vblocks * R, args, st);
+    });
+  });
+  return finalize_stats(rc, spart, vblocks, d, stats, st);
 }
 
 // ---- two-operand Linear  y = [a1 | a2] W^T + bias  (GraphConvLayer with use_init, large/ours.py:36-38) -------------
 extern "C" size_t sgf_gcn_epilogue_partial_bytes(int64_t n, int32_t d_out) {
-  if (n < 0 || d_out <= 0) return 0;
-  return static_cast<size_t>((n + 31) / 32) * 32 * static_cast<size_t>(d_out) * 2;
+  return n < 0 || d_out <= 0 ? 0 : tile_bytes(n, d_out);
 }
 
 // fp32 storage parks the first operand's product as a plain [n, d_out] fp32 matrix
@@ -1895,66 +1904,41 @@ extern "C" size_t sgf_gcn_epilogue_dtype_partial_bytes(int64_t n, int32_t d_out,
 extern "C" int sgf_gcn_epilogue_partial(const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias,
                                         int64_t n, int32_t d_in, int32_t d_out, int32_t dtype, void* partial,
                                         size_t partial_bytes, void* stream) {
-  int rc = check_common("sgf_gcn_epilogue_partial", a, lda, w, ldw, n, d_in, d_out, dtype, partial, d_out);
-  if (rc != SGF_OK) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(partial_bytes >= sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype), SGF_E_WORKSPACE,
-              "sgf_gcn_epilogue_partial: partial buffer %zu < %zu", partial_bytes,
-              sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype));
+  const char* fn = "sgf_gcn_epilogue_partial";
+  int rc = check_common(fn, a, lda, w, ldw, n, d_in, d_out, dtype, partial, d_out);
+  if (rc != SGF_OK || n == 0) return rc;
+  const size_t need = sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype);
+  SGF_REQUIRE(partial_bytes >= need, SGF_E_WORKSPACE, "%s: partial buffer %zu < %zu", fn, partial_bytes, need);
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (f32_storage(dtype))
-    return linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, bias, nullptr,
-                      0, nullptr, static_cast<float*>(partial), d_out, nullptr, static_cast<hipStream_t>(stream),
+    return linear_f32(fl(a), lda, n, d_in, d_out, fl(w), ldw, 1, bias, nullptr, 0, nullptr, fl(partial), d_out, nullptr, st,
                       dtype == SGF_F32_BF16X3);
-  RowGemmArgs args{static_cast<const uint16_t*>(a), lda, static_cast<const uint16_t*>(w), ldw, 0, bias, nullptr,
-                   nullptr, nullptr, 0, n, static_cast<uint4*>(partial)};
-  return launch_rowgemm<false, 1>(args, d_out, grid_blocks(n), static_cast<hipStream_t>(stream));
+  RowGemmArgs args{bf(a), lda, bf(w), ldw, 0, bias, nullptr, nullptr, nullptr, 0, n, static_cast<uint4*>(partial)};
+  return launch_rowgemm<false, 1>(fn, args, d_out, grid_blocks(n), st);
 }
 
 extern "C" int sgf_gcn_epilogue_stats_add(const void* a, int64_t lda, const void* w, int64_t ldw, const void* partial,
                                           size_t partial_bytes, int64_t n, int32_t d_in, int32_t d_out, int32_t dtype,
                                           void* y, int64_t ldy, const float* shift, float* stats, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-  int rc = check_common("sgf_gcn_epilogue_stats_add", a, lda, w, ldw, n, d_in, d_out, dtype, y, ldy);
+  const char* fn = "sgf_gcn_epilogue_stats_add";
+  int rc = check_common(fn, a, lda, w, ldw, n, d_in, d_out, dtype, y, ldy);
   if (rc != SGF_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (stats) SGF_CHECK_HIP(hipMemsetAsync(stats, 0, 2 * static_cast<size_t>(d_out) * sizeof(float), st));
-    return SGF_OK;
-  }
+  if (n == 0) return zero_stats(stats, d_out, st);
   SGF_REQUIRE(partial && reinterpret_cast<uintptr_t>(partial) % 16 == 0 &&
                   partial_bytes >= sgf_gcn_epilogue_dtype_partial_bytes(n, d_out, dtype),
-              SGF_E_INVALID, "sgf_gcn_epilogue_stats_add: partial buffer missing, misaligned or too small");
-  if (f32_storage(dtype)) {
-    float* spart = nullptr;
-    if (stats) {
-      SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
-                  "sgf_gcn_epilogue_stats_add: workspace too small");
-      spart = static_cast<float*>(workspace);
-    }
-    rc = linear_f32(static_cast<const float*>(a), lda, n, d_in, d_out, static_cast<const float*>(w), ldw, 1, nullptr,
-                    static_cast<const float*>(partial), d_out, shift, static_cast<float*>(y), ldy, spart, st,
-                    dtype == SGF_F32_BF16X3);
-    if (rc != SGF_OK || !stats) return rc;
-    hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, spart, linear_f32_blocks(n),
-                       2 * d_out, stats);
-    SGF_LAUNCH_CHECK();
-    return SGF_OK;
-  }
-  const int blocks = grid_blocks(n);
-  RowGemmArgs args{static_cast<const uint16_t*>(a), lda, static_cast<const uint16_t*>(w), ldw, 0, nullptr, shift,
-                   nullptr, static_cast<uint16_t*>(y), ldy, n,
-                   const_cast<uint4*>(static_cast<const uint4*>(partial))};
-  if (!stats) return launch_rowgemm<false, 2>(args, d_out, blocks, st);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
-              "sgf_gcn_epilogue_stats_add: workspace %zu < %zu", workspace_bytes,
-              sgf_gcn_epilogue_workspace_bytes(n, d_out));
-  args.spart = static_cast<float*>(workspace);
-  rc = launch_rowgemm<true, 2>(args, d_out, blocks, st);
+              SGF_E_INVALID, "%s: partial buffer missing, misaligned or too small", fn);
+  float* spart;
+  rc = stats_partials(fn, stats, workspace, workspace_bytes, n, d_out, &spart);
   if (rc != SGF_OK) return rc;
-  hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, args.spart, blocks, 2 * d_out,
-                     stats);
-  SGF_LAUNCH_CHECK();
-  return SGF_OK;
+  if (f32_storage(dtype))
+    return linear_f32_stats(a, lda, n, d_in, d_out, w, ldw, nullptr, partial, shift, y, ldy, spart, stats, dtype, st);
+  const int blocks = grid_blocks(n);
+  RowGemmArgs args{bf(a), lda, bf(w), ldw, 0, nullptr, shift, spart, bf(y), ldy, n,
+                   const_cast<uint4*>(static_cast<const uint4*>(partial))};
+  rc = !stats ? launch_rowgemm<false, 2>(fn, args, d_out, blocks, st) : launch_rowgemm<true, 2>(fn, args, d_out, blocks, st);
+  return finalize_stats(rc, spart, blocks, d_out, stats, st);
 }
 
 extern "C" int sgf_gcn_epilogue_apply(const void* y, int64_t ldy, const float* mean, const float* rstd,
@@ -1967,51 +1951,34 @@ extern "C" int sgf_gcn_epilogue_apply(const void* y, int64_t ldy, const float* m
 
 // ---- K10: both input stems from one read of the node features ----------------------------------------------------
 extern "C" int32_t sgf_stem_pair_supported(int32_t d_in, int32_t d_out, int32_t dtype) {
-  return dtype == SGF_BF16 && d_in > 0 && d_in % 4 == 0 && d_in <= kStemMaxK && (d_out == 64 || d_out == 128 || d_out == 256)
-             ? 1 : 0;
+  return d_in > 0 && d_in % 4 == 0 && d_in <= kStemMaxK && bf16_rows(d_out, dtype) ? 1 : 0;
 }
 
 extern "C" int sgf_stem_pair(const void* x, int64_t ldx, int64_t n, int32_t d_in, const void* w0, int64_t ldw0,
                              const float* bias0, const void* w1, int64_t ldw1, const float* bias1, int32_t d_out,
                              int32_t dtype, void* y0, int64_t ldy0, void* y1, int64_t ldy1, const float* shift0,
                              float* stats0, void* workspace, size_t workspace_bytes, void* stream) {
-  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "sgf_stem_pair: negative n");
+  const char* fn = "sgf_stem_pair";
+  SGF_REQUIRE(n >= 0, SGF_E_INVALID, "%s: negative n", fn);
   SGF_REQUIRE(sgf_stem_pair_supported(d_in, d_out, dtype), SGF_E_UNSUPPORTED,
-              "sgf_stem_pair: bf16 storage, d_in %% 4 == 0, d_in <= %d, d_out in {64, 128, 256} (got %d -> %d, dtype %d)",
+              "%s: bf16 storage, d_in %% 4 == 0, d_in <= %d, d_out in {64, 128, 256} (got %d -> %d, dtype %d)", fn,
               kStemMaxK, d_in, d_out, dtype);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (n == 0) {
-    if (stats0) SGF_CHECK_HIP(hipMemsetAsync(stats0, 0, 2 * static_cast<size_t>(d_out) * sizeof(float), st));
-    return SGF_OK;
-  }
-  SGF_REQUIRE(x && w0 && y0 && (!w1 || y1), SGF_E_INVALID, "sgf_stem_pair: null pointer");
+  if (n == 0) return zero_stats(stats0, d_out, st);
+  SGF_REQUIRE(x && w0 && y0 && (!w1 || y1), SGF_E_INVALID, "%s: null pointer", fn);
   SGF_REQUIRE(ldx >= d_in && ldx % 4 == 0 && reinterpret_cast<uintptr_t>(x) % 8 == 0 && ldw0 >= d_in && ldw0 % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(w0) % 8 == 0 &&
                   (!w1 || (ldw1 >= d_in && ldw1 % 4 == 0 && reinterpret_cast<uintptr_t>(w1) % 8 == 0)),
-              SGF_E_INVALID, "sgf_stem_pair: rows of x / W must be 8-byte aligned (pointers %% 8, leading dims %% 4 elements)");
-  SGF_REQUIRE(ldy0 >= d_out && ldy0 % 8 == 0 && reinterpret_cast<uintptr_t>(y0) % 16 == 0 &&
-                  (!w1 || (ldy1 >= d_out && ldy1 % 8 == 0 && reinterpret_cast<uintptr_t>(y1) % 16 == 0)),
-              SGF_E_INVALID, "sgf_stem_pair: rows of y must be 16-byte aligned");
+              SGF_E_INVALID, "%s: rows of x / W must be 8-byte aligned (pointers %% 8, leading dims %% 4 elements)", fn);
+  SGF_REQUIRE(ldy0 >= d_out && rows16(y0, ldy0) && (!w1 || (ldy1 >= d_out && rows16(y1, ldy1))), SGF_E_INVALID,
+              "%s: rows of y must be 16-byte aligned", fn);
+  float* spart;
+  int rc = stats_partials(fn, stats0, workspace, workspace_bytes, n, d_out, &spart);
+  if (rc != SGF_OK) return rc;
   const int blocks = grid_blocks(n);
-  StemArgs a{static_cast<const uint16_t*>(x), ldx, d_in, static_cast<const uint16_t*>(w0), ldw0, bias0,
-             static_cast<const uint16_t*>(w1), ldw1, bias1, shift0, nullptr, static_cast<uint16_t*>(y0), ldy0,
-             static_cast<uint16_t*>(y1), ldy1, n};
-  if (stats0) {
-    SGF_REQUIRE(workspace && workspace_bytes >= sgf_gcn_epilogue_workspace_bytes(n, d_out), SGF_E_WORKSPACE,
-                "sgf_stem_pair: workspace %zu < %zu", workspace_bytes, sgf_gcn_epilogue_workspace_bytes(n, d_out));
-    a.spart = static_cast<float*>(workspace);
-  }
-#define SGF_STEM(D_)                                                                                              \
-  if (stats0) hipLaunchKernelGGL((k_stem_bf16<D_, true>), dim3(blocks), dim3(kRgThreads), 0, st, a);               \
-  else hipLaunchKernelGGL((k_stem_bf16<D_, false>), dim3(blocks), dim3(kRgThreads), 0, st, a)
-  if (d_out == 64) { SGF_STEM(64); }
-  else if (d_out == 128) { SGF_STEM(128); }
-  else { SGF_STEM(256); }
-#undef SGF_STEM
-  SGF_LAUNCH_CHECK();
-  if (stats0) {
-    hipLaunchKernelGGL(k_rowgemm_stats, dim3((2 * d_out + 63) / 64), dim3(256), 0, st, a.spart, blocks, 2 * d_out, stats0);
-    SGF_LAUNCH_CHECK();
-  }
-  return SGF_OK;
+  StemArgs a{bf(x), ldx, d_in, bf(w0), ldw0, bias0, bf(w1), ldw1, bias1, shift0, spart, bf(y0), ldy0, bf(y1), ldy1, n};
+  rc = by_width(fn, d_out, [&](auto w_) {
+    return by_flag(stats0, [&](auto s) { return launch(k_stem_bf16<decltype(w_)::value, decltype(s)::value>, blocks, a, st); });
+  });
+  return finalize_stats(rc, spart, blocks, d_out, stats0, st);
 }

@@ -646,6 +646,27 @@ def test_stem_pair(stem, pair):
     assert stem.operands_untouched()
 
 
+# ---- no rows: the statistics are the empty sums, nothing else is read or written ----
+@pytest.mark.parametrize("d", [64, 256])
+@pytest.mark.parametrize("entry", ["sgf_gcn_epilogue_stats", "sgf_gcn_epilogue_stats_add", "sgf_gcn_epilogue_cat", "sgf_stem_pair"])
+def test_no_rows_zero_the_statistics(cuda, entry, d):
+    """n == 0 with a statistics pointer: every operand, output and workspace null; stats comes back as 2 d zero words between
+    its sentinels"""
+    L = _L()
+    buf = torch.full((2 * d + 2 * GAP,), SENTINEL, dtype=F32, device=cuda)
+    stats, st = ctypes.c_void_p(buf[GAP:].data_ptr()), _st(cuda)
+    if entry == "sgf_gcn_epilogue_stats":
+        L.call(entry, None, 0, None, 0, None, 0, d, d, L.SGF_BF16, None, 0, None, stats, None, 0, st)
+    elif entry == "sgf_gcn_epilogue_stats_add":
+        L.call(entry, None, 0, None, 0, None, 0, 0, d, d, L.SGF_BF16, None, 0, None, stats, None, 0, st)
+    elif entry == "sgf_gcn_epilogue_cat":
+        L.call(entry, None, 0, None, 0, None, 0, None, 0, d, L.SGF_BF16, None, 0, None, stats, None, 0, st)
+    else:
+        L.call(entry, None, 0, 0, 100, None, 0, None, None, 0, None, d, L.SGF_BF16, None, 0, None, 0, None, stats, None, 0, st)
+    assert bool((buf[GAP:GAP + 2 * d].view(torch.int32) == 0).all()), "the empty sums are not all zero words"
+    assert bool((buf[:GAP] == SENTINEL).all()) and bool((buf[GAP + 2 * d:] == SENTINEL).all()), "a word next to stats was written"
+
+
 # ---- sgf_combine_fc_fwd / _bwd and their _mapped / _g forms (csrc/head.hip) ----
 class HeadDev(Operands):
     def __init__(self, case, device):
