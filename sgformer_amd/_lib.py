@@ -15,6 +15,11 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsgf.so")
 SGF_F32 = 0
 SGF_BF16 = 1
 SGF_F32_BF16X3 = 2   # fp32 storage, matrix products as three bf16 products (include/sgf.h)
+SGF_OK = 0                 # status codes of the int-returning entries
+SGF_E_INVALID = -1         # bad argument (shape, alignment, dtype)
+SGF_E_WORKSPACE = -2       # workspace too small
+SGF_E_HIP = -3             # a HIP runtime call or kernel launch failed
+SGF_E_UNSUPPORTED = -4     # shape outside what the gfx950 kernels implement
 SGF_BCE_TARGET_F32 = 0     # target kinds of sgf_bce_fwd / _bwd: fp32 [n, c]
 SGF_BCE_TARGET_I64 = 1     # int64 0 / 1 [n, c]
 SGF_BCE_TARGET_CLASS = 2   # int64 class indices [n]
@@ -271,7 +276,7 @@ def available() -> bool:
 
 
 def check(rc: int, what: str):
-    if rc != 0:
+    if rc != SGF_OK:
         msg = load().sgf_last_error()
         raise SgfError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
 

@@ -10,8 +10,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .kernels import (HipKernels, LONG_ROW, _SEGMENT, _code, _ld, _one_pass_cat, _pair_gram, _ptr, _rows,  # noqa: F401
-                      _rows16, _stream, _workspace, _workspaces)
+from .kernels import HipKernels, LONG_ROW, _SEGMENT
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16

@@ -5,6 +5,7 @@ PyTorch supplies memory and streams only; a CPU tensor or a missing library rais
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional
 
 import torch
@@ -38,16 +39,24 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _stream_handle(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
 def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    return ctypes.c_void_p(_stream_handle(device))
+
+
+def _dtype_code(dtype) -> int:
+    if dtype == _F32:
+        return _lib.SGF_F32
+    if dtype == _BF16:
+        return _lib.SGF_BF16
+    raise TypeError(f"sgformer_amd kernels take float32 or bfloat16 storage, got {dtype}")
 
 
 def _code(t: torch.Tensor) -> int:
-    if t.dtype == _F32:
-        return _lib.SGF_F32
-    if t.dtype == _BF16:
-        return _lib.SGF_BF16
-    raise TypeError(f"sgformer_amd kernels take float32 or bfloat16 storage, got {t.dtype}")
+    return _dtype_code(t.dtype)
 
 
 # torch.set_float32_matmul_precision('high' | 'medium') (also set by torch.backends.cuda.matmul.allow_tf32 = True and by
@@ -154,21 +163,81 @@ def seed_scope():
     return _seed_scope
 
 
+def _fresh_bytes(device, nbytes: int) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
 def _workspace(device, name: str, nbytes: int) -> torch.Tensor:
     """Per-device, per-stream scratch reused across calls (users run on that stream, in order)."""
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         if _capture_scope is None:           # somebody else's capture: fresh scratch from ITS pool, not cached here
-            return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        ws = _capture_scope.get((device.index, name))
-        if ws is None or ws.numel() < nbytes:
-            ws = _capture_scope[(device.index, name)] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        return ws
-    key = (device.index, name, torch.cuda.current_stream(device).cuda_stream)
-    ws = _workspaces.get(key)
+            return _fresh_bytes(device, nbytes)
+        cache, key = _capture_scope, (device.index, name)
+    else:
+        cache, key = _workspaces, (device.index, name, _stream_handle(device))
+    ws = cache.get(key)
     if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
+        ws = cache[key] = _fresh_bytes(device, nbytes)
     return ws
+
+
+_NO_SCRATCH = (None, 0)
+
+_constant_bytes: "dict[str, int]" = {}
+
+
+def _const_bytes(query: str, *args) -> int:
+    """A byte count the library documents as constant (a block-partial buffer), asked once: the query is a measurable part
+    of the host cost of the loss on a mini-batch (profiles/kernel_table_host_cost.md).  For those two only -- other
+    *_workspace_bytes and *_supported answers depend on their arguments or on switches that sgf_reload_env() re-reads."""
+    n = _constant_bytes.get(query)
+    if n is None:
+        n = _constant_bytes[query] = int(getattr(_lib.load(), query)(*args))
+    return n
+
+
+def _scratch(device, name: Optional[str], nbytes: int):
+    """The (buffer, bytes) pair an entry takes as its scratch of `nbytes` for one call, to be spliced into _launch's
+    arguments.  With a name: the cached buffer of that name (_workspace) -- the name is part of the contract, entries that
+    run back to back share one on purpose and attn_h_bwd_pre leaves data in "attn_h_part" for attn_h_bwd_post.  With None:
+    taken from the caching allocator and given back after the call, for buffers that are large and rarely needed (the
+    once-per-graph plans, the evaluation metric).  An entry that needs none this time takes _NO_SCRATCH."""
+    ws = _fresh_bytes(device, nbytes) if name is None else _workspace(device, name, nbytes)
+    return ws, ws.numel()
+
+
+def _long_row_scratch(device, long_segments: int, d: int):
+    """The segment partials of the rows longer than LONG_ROW: one buffer for every SpMM family."""
+    if long_segments <= 0:
+        return _NO_SCRATCH
+    return _scratch(device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(long_segments, d))
+
+
+def _stats_scratch(device, n: int, d: int, want_stats: bool):
+    """The block partials of the BatchNorm column sums that the Linear epilogues form on request."""
+    if not want_stats:
+        return _NO_SCRATCH
+    return _scratch(device, "gcn_epi", _lib.load().sgf_gcn_epilogue_workspace_bytes(n, d))
+
+
+_PLAIN = frozenset((int, float, bool, type(None)))
+_Tensor = torch.Tensor
+
+
+def _launch(device, name: str, *args):
+    """Every call of a compute entry of libsgf leaves the package here: a tensor becomes its address and None stays the
+    null pointer (the entry's c_void_p parameter type, _lib.SIGNATURES, converts both), everything else (ints, floats,
+    ctypes arrays and byref, a pointer computed by hand) passes through, the current stream of `device` goes last.
+    Some entries sit on paths whose GPU work is a few microseconds at mini-batch sizes, so the host side is one pass
+    over the arguments (plain scalars, the majority, are recognised by their type alone; no ctypes object is built per
+    pointer) and one ctypes call, with no device context switch when the tensors' device is already current."""
+    argv = [a if type(a) in _PLAIN else (a.data_ptr() if isinstance(a, _Tensor) else a) for a in args]
+    argv.append(_stream_handle(device))
+    if torch.cuda.current_device() == device.index:
+        _lib.call(name, *argv)
+    else:
+        with torch.cuda.device(device):
+            _lib.call(name, *argv)
 
 
 def _rows16(t: torch.Tensor) -> torch.Tensor:
@@ -178,16 +247,12 @@ def _rows16(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-
 def _pair_gram() -> bool:
-    import os
     return os.environ.get("SGF_GRAM_PAIR", "1") != "0"
 
 
 def _one_pass_cat() -> bool:
-    import os
     return os.environ.get("SGF_GCN_CAT", "1") != "0"
-
 
 
 # ------------------------------------------------------------------------------------------------
@@ -215,11 +280,8 @@ class HipKernels:
         colind = torch.empty(nnz, dtype=torch.int32, device=dev)
         val = torch.empty(nnz, dtype=_F32, device=dev)
         deg = torch.empty(n, dtype=torch.int32, device=dev)
-        nbytes = _lib.load().sgf_csr_workspace_bytes(nnz, n)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_csr_build", _ptr(ei), nnz, n, _ptr(rowptr), _ptr(colind), _ptr(val),
-                      _ptr(deg), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_csr_build", ei, nnz, n, rowptr, colind, val, deg,
+                *_scratch(dev, None, _lib.load().sgf_csr_workspace_bytes(nnz, n)))
         return rowptr, colind, val, deg
 
     @staticmethod
@@ -229,12 +291,8 @@ class HipKernels:
         t_colind = torch.empty(nnz, dtype=torch.int32, device=dev)
         t_val = torch.empty(nnz, dtype=_F32, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        nbytes = _lib.load().sgf_csr_workspace_bytes(nnz, n)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_csr_transpose", _ptr(ei), nnz, n, _ptr(deg), _ptr(rowptr), _ptr(colind),
-                      _ptr(t_rowptr), _ptr(t_colind), _ptr(t_val), _ptr(flag), _ptr(ws), ws.numel(),
-                      _stream(dev))
+        _launch(dev, "sgf_csr_transpose", ei, nnz, n, deg, rowptr, colind, t_rowptr, t_colind, t_val, flag,
+                *_scratch(dev, None, _lib.load().sgf_csr_workspace_bytes(nnz, n)))
         return t_rowptr, t_colind, t_val, bool(int(flag.item()))  # one host sync, once per graph
 
     # ---- N1: induced subgraph ----
@@ -242,18 +300,14 @@ class HipKernels:
     def subgraph(ei: torch.Tensor, n: int, subset: torch.Tensor, relabel_nodes: bool, want_eid: bool):
         """ei int64 [2, nnz] and subset int64 [m] on the GPU -> (edge_index_sub [2, k], eid [k] | None)."""
         dev, nnz, m = ei.device, int(ei.shape[1]), int(subset.numel())
-        lib = _lib.load()
         relabel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         total = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws = _workspace(dev, "subgraph", lib.sgf_subgraph_workspace_bytes(nnz, n))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_subgraph_plan", _ptr(ei), nnz, n, _ptr(subset), m, _ptr(relabel), _ptr(total),
-                      _ptr(ws), ws.numel(), _stream(dev))
-            k = int(total.item())              # the one host sync: the output size
-            out = torch.empty((2, k), dtype=torch.int64, device=dev)
-            eid = torch.empty(k, dtype=torch.int64, device=dev) if want_eid else None
-            _lib.call("sgf_subgraph_emit", _ptr(ei), nnz, n, _ptr(relabel), int(relabel_nodes), k, _ptr(out),
-                      _ptr(eid), _ptr(ws), ws.numel(), _stream(dev))
+        scratch = _scratch(dev, "subgraph", _lib.load().sgf_subgraph_workspace_bytes(nnz, n))
+        _launch(dev, "sgf_subgraph_plan", ei, nnz, n, subset, m, relabel, total, *scratch)
+        k = int(total.item())              # the one host sync: the output size
+        out = torch.empty((2, k), dtype=torch.int64, device=dev)
+        eid = torch.empty(k, dtype=torch.int64, device=dev) if want_eid else None
+        _launch(dev, "sgf_subgraph_emit", ei, nnz, n, relabel, int(relabel_nodes), k, out, eid, *scratch)
         return out, eid
 
     @staticmethod
@@ -266,25 +320,23 @@ class HipKernels:
         rowptr_b = torch.empty(m + 1, dtype=torch.int64, device=dev)
         deg_b = torch.empty(m + 1, dtype=torch.int32, device=dev)
         total = torch.empty(3, dtype=torch.int64, device=dev)
-        ws = _workspace(dev, "subgraph_csr_plan", lib.sgf_subgraph_csr_plan_workspace_bytes(m))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_subgraph_csr_plan", _ptr(rowptr), _ptr(colind), n, _ptr(subset), m, _ptr(local_of), _ptr(rowptr_b),
-                      _ptr(deg_b), _ptr(total), _ptr(ws), ws.numel(), _stream(dev))
-            # the plan MARKED the parent's shared `local_of` table; only the emit call clears the marks again.  Whatever fails
-            # in between (the host read, an allocation) must not leave them behind: later batches would pick up stale local
-            # ids for nodes outside their subset.
-            try:
-                t, bad, longest = total.tolist()            # the one host read of the batch
-                t = 0 if bad else int(t)
-                colind_b = torch.empty(t, dtype=torch.int32, device=dev)
-                val_b = torch.empty(t, dtype=_F32, device=dev)
-                ei_b = torch.empty((2, t), dtype=torch.int64, device=dev) if want_edges else None
-                ws2 = _workspace(dev, "subgraph_csr_emit", lib.sgf_subgraph_csr_emit_workspace_bytes(m, t))
-            except BaseException:
-                local_of.fill_(-1)
-                raise
-            _lib.call("sgf_subgraph_csr_emit", _ptr(rowptr), _ptr(colind), n, _ptr(subset), m, _ptr(local_of), _ptr(rowptr_b),
-                      _ptr(deg_b), t, _ptr(colind_b), _ptr(val_b), _ptr(ei_b), _ptr(ws2), ws2.numel(), _stream(dev))
+        _launch(dev, "sgf_subgraph_csr_plan", rowptr, colind, n, subset, m, local_of, rowptr_b, deg_b, total,
+                *_scratch(dev, "subgraph_csr_plan", lib.sgf_subgraph_csr_plan_workspace_bytes(m)))
+        # the plan MARKED the parent's shared `local_of` table; only the emit call clears the marks again.  Whatever fails
+        # in between (the host read, an allocation) must not leave them behind: later batches would pick up stale local
+        # ids for nodes outside their subset.
+        try:
+            t, bad, longest = total.tolist()            # the one host read of the batch
+            t = 0 if bad else int(t)
+            colind_b = torch.empty(t, dtype=torch.int32, device=dev)
+            val_b = torch.empty(t, dtype=_F32, device=dev)
+            ei_b = torch.empty((2, t), dtype=torch.int64, device=dev) if want_edges else None
+            scratch = _scratch(dev, "subgraph_csr_emit", lib.sgf_subgraph_csr_emit_workspace_bytes(m, t))
+        except BaseException:
+            local_of.fill_(-1)
+            raise
+        _launch(dev, "sgf_subgraph_csr_emit", rowptr, colind, n, subset, m, local_of, rowptr_b, deg_b, t, colind_b, val_b,
+                ei_b, *scratch)
         if bad:
             return None
         return rowptr_b, colind_b, val_b, deg_b[:m], ei_b, int(longest)
@@ -305,10 +357,9 @@ class HipKernels:
         colind_b = torch.empty(max(edge_cap, 1), dtype=torch.int32, device=dev)
         val_b = torch.empty(max(edge_cap, 1), dtype=_F32, device=dev)
         deg_b = torch.empty(node_cap + 1, dtype=torch.int32, device=dev)
-        ws = _workspace(dev, "sampled_csr_build", _lib.load().sgf_sampled_csr_build_workspace_bytes(node_cap, edge_cap))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_sampled_csr_build", _ptr(e_src), _ptr(e_dst), _ptr(counts), node_cap, edge_cap, int(max_fanout),
-                      _ptr(rowptr_b), _ptr(colind_b), _ptr(val_b), _ptr(deg_b), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_sampled_csr_build", e_src, e_dst, counts, node_cap, edge_cap, int(max_fanout), rowptr_b, colind_b,
+                val_b, deg_b,
+                *_scratch(dev, "sampled_csr_build", _lib.load().sgf_sampled_csr_build_workspace_bytes(node_cap, edge_cap)))
         return rowptr_b, colind_b, val_b, deg_b
 
     @staticmethod
@@ -319,26 +370,20 @@ class HipKernels:
         t_rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
         t_colind = torch.empty(nnz, dtype=torch.int32, device=dev)
         t_val = torch.empty(nnz, dtype=_F32, device=dev)
-        ws = _workspace(dev, "sampled_csr_transpose", _lib.load().sgf_sampled_csr_transpose_workspace_bytes(n, nnz))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_sampled_csr_transpose", _ptr(rowptr), _ptr(colind), _ptr(val), n, nnz, _ptr(t_rowptr), _ptr(t_colind),
-                      _ptr(t_val), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_sampled_csr_transpose", rowptr, colind, val, n, nnz, t_rowptr, t_colind, t_val,
+                *_scratch(dev, "sampled_csr_transpose", _lib.load().sgf_sampled_csr_transpose_workspace_bytes(n, nnz)))
         return t_rowptr, t_colind, t_val
 
     # ---- N2: trainer prologue (to_undirected / remove_self_loops / add_self_loops) ----
     @staticmethod
     def graph_prologue(ei: torch.Tensor, n: int, undirected: bool, remove_loops: bool, add_loops: bool):
         dev, m = ei.device, int(ei.shape[1])
-        lib = _lib.load()
         total = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(lib.sgf_graph_prologue_workspace_bytes(m, n), 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_graph_prologue_plan", _ptr(ei), m, n, int(undirected), int(remove_loops), int(add_loops),
-                      _ptr(total), _ptr(ws), ws.numel(), _stream(dev))
-            k = int(total.item())              # the one host sync: the output size
-            out = torch.empty((2, k), dtype=torch.int64, device=dev)
-            _lib.call("sgf_graph_prologue_emit", m, n, int(undirected), int(add_loops), k, _ptr(out), _ptr(ws),
-                      ws.numel(), _stream(dev))
+        scratch = _scratch(dev, None, _lib.load().sgf_graph_prologue_workspace_bytes(m, n))
+        _launch(dev, "sgf_graph_prologue_plan", ei, m, n, int(undirected), int(remove_loops), int(add_loops), total, *scratch)
+        k = int(total.item())              # the one host sync: the output size
+        out = torch.empty((2, k), dtype=torch.int64, device=dev)
+        _launch(dev, "sgf_graph_prologue_emit", m, n, int(undirected), int(add_loops), k, out, *scratch)
         return out
 
     # ---- T2 ----
@@ -357,16 +402,12 @@ class HipKernels:
             raise ValueError("spmm: `out` must be [n_rows, d], same dtype, row-contiguous and 4-element aligned")
         if n_rows == 0 or d == 0:
             return y
-        with torch.cuda.device(x.device):
-            if long_segments > 0 or stream_hint:
-                ws = (_workspace(x.device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(long_segments, d))
-                      if long_segments > 0 else None)
-                _lib.call("sgf_spmm_stream" if stream_hint else "sgf_spmm_split", _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(x), x.stride(0), x.shape[0],
-                          _ptr(y), y.stride(0), n_rows, d, _code(x), LONG_ROW, long_segments, _ptr(ws),
-                          0 if ws is None else ws.numel(), _stream(x.device))
-            else:
-                _lib.call("sgf_spmm", _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(x), x.stride(0), x.shape[0],
-                          _ptr(y), y.stride(0), n_rows, d, _code(x), _stream(x.device))
+        if long_segments > 0 or stream_hint:
+            _launch(x.device, "sgf_spmm_stream" if stream_hint else "sgf_spmm_split", rowptr, colind, val, x, x.stride(0),
+                    x.shape[0], y, y.stride(0), n_rows, d, _code(x), LONG_ROW, long_segments,
+                    *_long_row_scratch(x.device, long_segments, d))
+        else:
+            _launch(x.device, "sgf_spmm", rowptr, colind, val, x, x.stride(0), x.shape[0], y, y.stride(0), n_rows, d, _code(x))
         return y
 
     # ---- T2 gathering zero-elided operand rows (bf16, d = 256; csrc/spmm.hip: k_spmm_row_packed) ----
@@ -375,9 +416,9 @@ class HipKernels:
         """Would sgf_spmm_packed gather the slots for a contiguous operand of this shape (else it runs sgf_spmm_split's
         kernels on the dense rows)?  The launcher's own rule, SGF_SPMM_PACKED included."""
         n, d = int(x_shape[0]), int(x_shape[1])
-        if dtype != torch.bfloat16 or n == 0:
+        if dtype != _BF16 or n == 0:
             return False
-        return bool(_lib.load().sgf_spmm_packed_supported(d, _lib.SGF_BF16, d, d, n, 1, int(slot_bytes)))
+        return bool(_lib.load().sgf_spmm_packed_supported(d, _dtype_code(dtype), d, d, n, 1, int(slot_bytes)))
 
     @staticmethod
     def spmm_packed(rowptr, colind, val, x: torch.Tensor, packed: "PackedRows", n_rows: int, long_segments: int = 0) -> torch.Tensor:
@@ -390,12 +431,9 @@ class HipKernels:
         y = torch.empty((n_rows, d), dtype=x.dtype, device=x.device)
         if n_rows == 0 or d == 0:
             return y
-        with torch.cuda.device(x.device):
-            ws = (_workspace(x.device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(long_segments, d))
-                  if long_segments > 0 else None)
-            _lib.call("sgf_spmm_packed", _ptr(rowptr), _ptr(colind), _ptr(val), _ptr(x), x.stride(0), x.shape[0],
-                      _ptr(packed.slots), packed.slot_bytes, _ptr(packed.overflow), _ptr(y), y.stride(0), n_rows, d, _code(x),
-                      LONG_ROW, long_segments, _ptr(ws), 0 if ws is None else ws.numel(), _stream(x.device))
+        _launch(x.device, "sgf_spmm_packed", rowptr, colind, val, x, x.stride(0), x.shape[0], packed.slots, packed.slot_bytes,
+                packed.overflow, y, y.stride(0), n_rows, d, _code(x), LONG_ROW, long_segments,
+                *_long_row_scratch(x.device, long_segments, d))
         counters["spmm_packed"] += 1
         return y
 
@@ -407,11 +445,8 @@ class HipKernels:
         perm = torch.empty(n, dtype=torch.int32, device=dev)
         inv = torch.empty(n, dtype=torch.int32, device=dev)
         comm = torch.empty(n, dtype=torch.int32, device=dev)
-        nbytes = _lib.load().sgf_reorder_workspace_bytes(nnz, n)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_reorder", _ptr(ei), nnz, n, int(iters1), int(iters2), _ptr(perm), _ptr(inv),
-                      _ptr(comm), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_reorder", ei, nnz, n, int(iters1), int(iters2), perm, inv, comm,
+                *_scratch(dev, None, _lib.load().sgf_reorder_workspace_bytes(nnz, n)))
         return perm, inv, comm
 
     @staticmethod
@@ -424,12 +459,9 @@ class HipKernels:
         sh_ptr = torch.empty(nb + 1, dtype=torch.int32, device=dev)
         sh_cols = torch.empty(max(nb * lds_rows, 1), dtype=torch.int32, device=dev)
         stats = torch.zeros(4, dtype=torch.int64, device=dev)
-        nbytes = _lib.load().sgf_spmm_plan_workspace_bytes(nnz, n, rows_per_block)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_spmm_plan", _ptr(rowptr), _ptr(colind), _ptr(val), n, nnz, int(rows_per_block),
-                      int(lds_rows), int(long_len), _ptr(ecode), _ptr(ev), _ptr(nlds), _ptr(sh_ptr),
-                      _ptr(sh_cols), _ptr(stats), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_spmm_plan", rowptr, colind, val, n, nnz, int(rows_per_block), int(lds_rows), int(long_len), ecode, ev,
+                nlds, sh_ptr, sh_cols, stats,
+                *_scratch(dev, None, _lib.load().sgf_spmm_plan_workspace_bytes(nnz, n, rows_per_block)))
         st = [int(v) for v in stats.tolist()]                      # one host sync, once per plan
         return ecode, ev, nlds, sh_ptr, sh_cols[: max(st[1], 1)].clone(), st
 
@@ -441,20 +473,15 @@ class HipKernels:
         y = torch.empty((n_rows, d), dtype=x.dtype, device=x.device) if out is None else out
         if n_rows == 0 or d == 0:
             return y
-        with torch.cuda.device(x.device):
-            ws = None
-            if long_segments > 0:
-                ws = _workspace(x.device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(long_segments, d))
-            _lib.call("sgf_spmm_blocked", _ptr(rowptr), _ptr(plan.ecode), _ptr(plan.eval), _ptr(plan.nlds),
-                      _ptr(plan.sh_ptr), _ptr(plan.sh_cols), _ptr(x), x.stride(0), _ptr(y), y.stride(0), n_rows, d,
-                      _code(x), plan.rows_per_block, plan.lds_rows, LONG_ROW, long_segments, _ptr(ws),
-                      0 if ws is None else ws.numel(), _stream(x.device))
+        _launch(x.device, "sgf_spmm_blocked", rowptr, plan.ecode, plan.eval, plan.nlds, plan.sh_ptr, plan.sh_cols, x, x.stride(0),
+                y, y.stride(0), n_rows, d, _code(x), plan.rows_per_block, plan.lds_rows, LONG_ROW, long_segments,
+                *_long_row_scratch(x.device, long_segments, d))
         return y
 
     # ---- T2 on a re-ordered graph: dense matrix-core tiles + gather remainder (csrc/spmm_tile.hip) ----
     @staticmethod
     def tile_supported(d: int, dtype) -> bool:
-        return bool(_lib.load().sgf_spmm_tile_supported(int(d), _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+        return dtype in (_BF16, _F32) and bool(_lib.load().sgf_spmm_tile_supported(int(d), _dtype_code(dtype)))
 
     @staticmethod
     def tile_blocks(comm_sorted: Optional[torch.Tensor], n: int, max_rows: int, device) -> torch.Tensor:
@@ -462,9 +489,7 @@ class HipKernels:
         cap = 4 * n // int(max_rows) + 4
         blk = torch.empty(cap + 1, dtype=torch.int32, device=device)
         nb = ctypes.c_int64(0)
-        with torch.cuda.device(device):
-            _lib.call("sgf_spmm_tile_blocks", _ptr(comm_sorted), n, int(max_rows), _ptr(blk), cap, ctypes.byref(nb),
-                      _stream(device))
+        _launch(device, "sgf_spmm_tile_blocks", comm_sorted, n, int(max_rows), blk, cap, ctypes.byref(nb))
         return blk[: nb.value + 1].clone()
 
     @staticmethod
@@ -479,22 +504,18 @@ class HipKernels:
         tile_ptr = torch.empty(nb + 1, dtype=torch.int64, device=dev)
         rem_rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
         stats = torch.zeros(8, dtype=torch.int64, device=dev)
-        nbytes = _lib.load().sgf_spmm_tile_plan_workspace_bytes(nnz, n, nb)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_spmm_tile_plan", _ptr(rowptr), _ptr(colind), _ptr(val), n, nnz, _ptr(blk_row), nb, int(cap),
-                      int(min_count), int(long_len), _ptr(ecode), _ptr(ev), _ptr(nlds), _ptr(sh_ptr), _ptr(sh_cols),
-                      _ptr(tile_ptr), _ptr(rem_rowptr), _ptr(stats), _ptr(ws), ws.numel(), _stream(dev))
-            st = [int(v) for v in stats.tolist()]                      # one host sync, once per plan
-            del ws
-            if st[7]:
-                raise ValueError("tile_plan: a row block is empty or longer than 256 rows")
-            n_frag, n_rem = st[4], st[5]
-            tiles = torch.empty(max(n_frag, 1) * 512, dtype=torch.int32, device=dev)     # 2 KiB per fragment
-            rem_col = torch.empty(max(n_rem, 1), dtype=torch.int32, device=dev)
-            rem_val = torch.empty(max(n_rem, 1), dtype=_F32, device=dev)
-            _lib.call("sgf_spmm_tile_fill", _ptr(rowptr), _ptr(ecode), _ptr(ev), _ptr(nlds), n, nnz, _ptr(blk_row), nb,
-                      _ptr(tile_ptr), n_frag, _ptr(rem_rowptr), _ptr(tiles), _ptr(rem_col), _ptr(rem_val), _stream(dev))
+        _launch(dev, "sgf_spmm_tile_plan", rowptr, colind, val, n, nnz, blk_row, nb, int(cap), int(min_count), int(long_len),
+                ecode, ev, nlds, sh_ptr, sh_cols, tile_ptr, rem_rowptr, stats,
+                *_scratch(dev, None, _lib.load().sgf_spmm_tile_plan_workspace_bytes(nnz, n, nb)))
+        st = [int(v) for v in stats.tolist()]                      # one host sync, once per plan; the scratch is free again
+        if st[7]:
+            raise ValueError("tile_plan: a row block is empty or longer than 256 rows")
+        n_frag, n_rem = st[4], st[5]
+        tiles = torch.empty(max(n_frag, 1) * 512, dtype=torch.int32, device=dev)     # 2 KiB per fragment
+        rem_col = torch.empty(max(n_rem, 1), dtype=torch.int32, device=dev)
+        rem_val = torch.empty(max(n_rem, 1), dtype=_F32, device=dev)
+        _launch(dev, "sgf_spmm_tile_fill", rowptr, ecode, ev, nlds, n, nnz, blk_row, nb, tile_ptr, n_frag, rem_rowptr, tiles,
+                rem_col, rem_val)
         return sh_ptr, sh_cols[: max(st[1], 1)].clone(), tile_ptr, tiles, rem_rowptr, rem_col, rem_val, st
 
     @staticmethod
@@ -505,14 +526,11 @@ class HipKernels:
         ng = n_frag // 2
         grp = torch.zeros((max(ng, 1), 2), dtype=torch.int32, device=dev)
         units = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(_lib.load().sgf_spmm_tile_pack_workspace_bytes(n_frag), 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_spmm_tile_pack_layout", _ptr(blk_row), nb, _ptr(tile_ptr), _ptr(tiles), n_frag, _ptr(grp),
-                      _ptr(units), _ptr(ws), ws.numel(), _stream(dev))
-            nu = int(units.item())                                      # one host sync, once per plan
-            pool = torch.zeros(nu * 16 + 4096, dtype=torch.uint8, device=dev)   # the kernel fetches whole KiB
-            _lib.call("sgf_spmm_tile_pack", _ptr(blk_row), nb, _ptr(tile_ptr), _ptr(tiles), n_frag, _ptr(grp), _ptr(pool),
-                      nu, _stream(dev))
+        _launch(dev, "sgf_spmm_tile_pack_layout", blk_row, nb, tile_ptr, tiles, n_frag, grp, units,
+                *_scratch(dev, None, _lib.load().sgf_spmm_tile_pack_workspace_bytes(n_frag)))
+        nu = int(units.item())                                      # one host sync, once per plan
+        pool = torch.zeros(nu * 16 + 4096, dtype=torch.uint8, device=dev)   # the kernel fetches whole KiB
+        _launch(dev, "sgf_spmm_tile_pack", blk_row, nb, tile_ptr, tiles, n_frag, grp, pool, nu)
         return grp, pool, nu
 
     @staticmethod
@@ -523,19 +541,15 @@ class HipKernels:
         if n_rows == 0 or d == 0:
             return y
         segs = plan.long_segments
-        with torch.cuda.device(x.device):
-            ws = None
-            if segs > 0:
-                ws = _workspace(x.device, "spmm_long", _lib.load().sgf_spmm_split_workspace_bytes(segs, d))
-            _lib.call("sgf_spmm_tile", _ptr(plan.blk_row), plan.nb, plan.block_rows, _ptr(plan.sh_ptr), _ptr(plan.sh_cols),
-                      _ptr(plan.tile_ptr), _ptr(plan.grp), _ptr(plan.pool), _ptr(plan.rem_rowptr), _ptr(plan.rem_col),
-                      _ptr(plan.rem_val), _ptr(x), x.stride(0), x.shape[0], _ptr(y), y.stride(0), n_rows, d, _code(x),
-                      LONG_ROW, segs, _ptr(ws), 0 if ws is None else ws.numel(), _stream(x.device))
+        _launch(x.device, "sgf_spmm_tile", plan.blk_row, plan.nb, plan.block_rows, plan.sh_ptr, plan.sh_cols, plan.tile_ptr,
+                plan.grp, plan.pool, plan.rem_rowptr, plan.rem_col, plan.rem_val, x, x.stride(0), x.shape[0], y, y.stride(0),
+                n_rows, d, _code(x), LONG_ROW, segs, *_long_row_scratch(x.device, segs, d))
         return y
 
     @staticmethod
     def lds_rows_max(dtype) -> int:
-        return int(_lib.load().sgf_spmm_lds_rows_len(_lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+        code = _dtype_code(dtype)
+        return int(_lib.load().sgf_spmm_lds_rows_len(code))
 
     @staticmethod
     def gather_rows(src: torch.Tensor, idx: torch.Tensor, out_dtype=None) -> torch.Tensor:
@@ -544,10 +558,8 @@ class HipKernels:
             src = src.contiguous()
         n_out, d = int(idx.numel()), src.shape[1]
         out = torch.empty((n_out, d), dtype=out_dtype or src.dtype, device=src.device)
-        with torch.cuda.device(src.device):
-            _lib.call("sgf_gather_rows", _ptr(src), src.stride(0), _code(src), src.shape[0], _ptr(idx),
-                      int(idx.dtype == torch.int64), n_out, d, _ptr(out), out.stride(0), _code(out),
-                      _stream(src.device))
+        _launch(src.device, "sgf_gather_rows", src, src.stride(0), _code(src), src.shape[0], idx, int(idx.dtype == torch.int64),
+                n_out, d, out, out.stride(0), _code(out))
         return out
 
     @staticmethod
@@ -559,10 +571,8 @@ class HipKernels:
         n_out = int(src.shape[0] if idx is None else idx.numel())
         d = src.shape[1]
         out = torch.empty((n_out, d_pad), dtype=out_dtype or src.dtype, device=src.device)
-        with torch.cuda.device(src.device):
-            _lib.call("sgf_pad_rows", _ptr(src), src.stride(0), _code(src), src.shape[0], _ptr(idx),
-                      int(idx is not None and idx.dtype == torch.int64), n_out, d, d_pad, _ptr(out), out.stride(0),
-                      _code(out), _stream(src.device))
+        _launch(src.device, "sgf_pad_rows", src, src.stride(0), _code(src), src.shape[0], idx,
+                int(idx is not None and idx.dtype == torch.int64), n_out, d, d_pad, out, out.stride(0), _code(out))
         return out
 
     # ---- T4: the general Linear (any shape, any alignment; csrc/gemm.hip) ----
@@ -582,11 +592,9 @@ class HipKernels:
             raise RuntimeError("gemm: out must have contiguous rows")
         if addend is not None and (addend.stride(-1) != 1 and n > 1):
             addend = addend.contiguous()
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gemm", _ptr(a), a.stride(0), a.stride(1), _code(a), _ptr(b), b.stride(0), b.stride(1), _code(b),
-                      m, n, k, float(alpha), _ptr(alpha_dev), _ptr(bias), float(beta), _ptr(addend),
-                      0 if addend is None else max(addend.stride(0), n), 0 if addend is None else _code(addend),
-                      _ptr(out), max(out.stride(0), n), _code(out), _stream(dev))
+        _launch(dev, "sgf_gemm", a, a.stride(0), a.stride(1), _code(a), b, b.stride(0), b.stride(1), _code(b), m, n, k,
+                float(alpha), alpha_dev, bias, float(beta), addend, 0 if addend is None else max(addend.stride(0), n),
+                0 if addend is None else _code(addend), out, max(out.stride(0), n), _code(out))
         return out
 
     # ---- T3: the d x d algebra of the attention as one call each way (csrc/attn_small.hip) ----
@@ -596,19 +604,17 @@ class HipKernels:
         projections' fp32 weights [d, D] / biases [d] (wv None: V = h)."""
         d, D = wq.shape
         dev = G.device
-        lib = _lib.load()
-        ws = [t if (t is None or (t.dtype == _F32 and t.is_contiguous())) else t.float().contiguous()
+        wb = [t if (t is None or (t.dtype == _F32 and t.is_contiguous())) else t.float().contiguous()
               for t in (wq, bq, wk, bk, wv, bv)]
         G = G if (G.dtype == _F32 and G.stride(-1) == 1) else G.float().contiguous()
         s = s if (s.dtype == _F32 and s.is_contiguous()) else s.float().contiguous()
         M = torch.empty((D, d), dtype=_F32, device=dev)
         mwb = torch.empty(d + D + 1, dtype=_F32, device=dev)
-        saved = torch.empty(lib.sgf_attn_h_small_saved_bytes(D, d), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_small_fwd", _ptr(G), G.stride(0), _ptr(s), float(n_rows), float(n_total), _ptr(ws[0]),
-                      _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]), _ptr(ws[4]), _ptr(ws[5]), D, D, d, _ptr(M), d,
-                      _ptr(mwb[:d]), _ptr(mwb[d:d + D]), _ptr(mwb[d + D:]), _ptr(saved), saved.numel(), _stream(dev))
-        return M, mwb[:d], mwb[d:d + D], mwb[d + D:], saved
+        saved = torch.empty(_lib.load().sgf_attn_h_small_saved_bytes(D, d), dtype=torch.uint8, device=dev)
+        m, w, beta = mwb[:d], mwb[d:d + D], mwb[d + D:]
+        _launch(dev, "sgf_attn_h_small_fwd", G, G.stride(0), s, float(n_rows), float(n_total), *wb, D, D, d, M, d, m, w, beta,
+                saved, saved.numel())
+        return M, m, w, beta, saved
 
     @staticmethod
     def attn_h_small_bwd(dM, dw, dm, dbeta, n_total: float, saved, d_in: int, d_out: int, want_v: bool = True):
@@ -616,18 +622,15 @@ class HipKernels:
         M, w, m, beta (the blocks of hstats) and what attn_h_small_fwd saved."""
         D, d = d_in, d_out
         dev = dM.device
-        lib = _lib.load()
-        ws = _workspace(dev, "attn_small", lib.sgf_attn_h_small_workspace_bytes(D, d))
+        scratch = _scratch(dev, "attn_small", _lib.load().sgf_attn_h_small_workspace_bytes(D, d))
         Dm = torch.empty((D, D), dtype=_F32, device=dev)
         ds = torch.empty(D, dtype=_F32, device=dev)
         gw = torch.empty((3 if want_v else 2, d, D), dtype=_F32, device=dev)
         gb = torch.empty((3 if want_v else 2, d), dtype=_F32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_small_bwd", _ptr(dM), dM.stride(0), _ptr(dw), _ptr(dm), _ptr(dbeta), float(n_total), D, d,
-                      _ptr(saved), saved.numel(), _ptr(Dm), D, _ptr(ds), _ptr(gw[0]), _ptr(gb[0]), _ptr(gw[1]), _ptr(gb[1]),
-                      _ptr(gw[2]) if want_v else None, _ptr(gb[2]) if want_v else None, D, _ptr(ws), ws.numel(),
-                      _stream(dev))
-        return Dm, ds, gw[0], gb[0], gw[1], gb[1], (gw[2] if want_v else None), (gb[2] if want_v else None)
+        gwv, gbv = (gw[2], gb[2]) if want_v else (None, None)
+        _launch(dev, "sgf_attn_h_small_bwd", dM, dM.stride(0), dw, dm, dbeta, float(n_total), D, d, saved, saved.numel(), Dm, D,
+                ds, gw[0], gb[0], gw[1], gb[1], gwv, gbv, D, *scratch)
+        return Dm, ds, gw[0], gb[0], gw[1], gb[1], gwv, gbv
 
     # ---- T3 ----  q, k: [n, H*d] views (ld = stride(0)); v: [n, Hv*d]
     @staticmethod
@@ -635,10 +638,8 @@ class HipKernels:
         n, dev = q.shape[0], q.device
         lib = _lib.load()
         stats = torch.empty(lib.sgf_attn_stats_len(heads, d), dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", lib.sgf_attn_workspace_bytes(n, heads, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_fwd_reduce", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), n,
-                      heads, v_heads, d, _code(q), _ptr(stats), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_attn_fwd_reduce", q, _ld(q), k, _ld(k), v, _ld(v), n, heads, v_heads, d, _code(q), stats,
+                *_scratch(dev, "attn", lib.sgf_attn_workspace_bytes(n, heads, d)))
         return stats
 
     @staticmethod
@@ -647,10 +648,8 @@ class HipKernels:
         out = torch.empty((n, d), dtype=q.dtype, device=dev)
         den = torch.empty((n, heads), dtype=_F32, device=dev)
         o_heads = torch.empty((n, heads * d), dtype=q.dtype, device=dev) if heads > 1 else None
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_fwd_apply", _ptr(q), _ld(q), _ptr(v), _ld(v), n, float(n_total),
-                      heads, v_heads, d, _code(q), _ptr(stats), _ptr(out), out.stride(0), _ptr(den),
-                      _ptr(o_heads), _stream(dev))
+        _launch(dev, "sgf_attn_fwd_apply", q, _ld(q), v, _ld(v), n, float(n_total), heads, v_heads, d, _code(q), stats, out,
+                out.stride(0), den, o_heads)
         return out, den, o_heads
 
     @staticmethod
@@ -659,11 +658,8 @@ class HipKernels:
         n, dev = q.shape[0], q.device
         lib = _lib.load()
         bstats = torch.empty(lib.sgf_attn_bstats_len(heads, d), dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", lib.sgf_attn_workspace_bytes(n, heads, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_bwd_reduce_heads" if per_head else "sgf_attn_bwd_reduce", _ptr(q), _ld(q), _ptr(g), _ld(g), _ptr(o), _ld(o),
-                      _ptr(den), n, heads, d, _code(q), _ptr(bstats), _ptr(ws), ws.numel(),
-                      _stream(dev))
+        _launch(dev, "sgf_attn_bwd_reduce_heads" if per_head else "sgf_attn_bwd_reduce", q, _ld(q), g, _ld(g), o, _ld(o), den, n,
+                heads, d, _code(q), bstats, *_scratch(dev, "attn", lib.sgf_attn_workspace_bytes(n, heads, d)))
         return bstats
 
     @staticmethod
@@ -671,11 +667,9 @@ class HipKernels:
                        d: int, dq, dk, dv, per_head: bool = False):
         """Writes dq, dk, dv (views with row stride = stride(0)) in place."""
         n, dev = q.shape[0], q.device
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_bwd_apply_heads" if per_head else "sgf_attn_bwd_apply", _ptr(q), _ld(q), _ptr(k), _ld(k), _ptr(v), _ld(v), _ptr(g),
-                      _ld(g), _ptr(o), _ld(o), _ptr(den), n, float(n_total), heads, v_heads, d,
-                      _code(q), _ptr(stats), _ptr(bstats), _ptr(dq), _ld(dq), _ptr(dk), _ld(dk),
-                      _ptr(dv), _ld(dv), _stream(dev))
+        _launch(dev, "sgf_attn_bwd_apply_heads" if per_head else "sgf_attn_bwd_apply", q, _ld(q), k, _ld(k), v, _ld(v), g, _ld(g),
+                o, _ld(o), den, n, float(n_total), heads, v_heads, d, _code(q), stats, bstats, dq, _ld(dq), dk, _ld(dk), dv,
+                _ld(dv))
 
     # ---- T3+T4 fused: attention from the un-projected input (H = 1) ----
     @staticmethod
@@ -684,9 +678,8 @@ class HipKernels:
         dev = h.device
         out = torch.empty((n, d), dtype=h.dtype, device=dev)
         den = torch.empty((n, 1), dtype=_F32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_fwd", _ptr(h), _ld(h), n, d, _mm_code(h, "sgf_attn_h_supported", d), _ptr(M), _ptr(m), _ptr(w),
-                      _ptr(beta), _ptr(out), out.stride(0), _ptr(den), _stream(dev))
+        _launch(dev, "sgf_attn_h_fwd", h, _ld(h), n, d, _mm_code(h, "sgf_attn_h_supported", d), M, m, w, beta, out,
+                out.stride(0), den)
         return out, den
 
     @staticmethod
@@ -695,10 +688,9 @@ class HipKernels:
         dev = h.device
         lib = _lib.load()
         hstats = torch.empty(lib.sgf_attn_h_bstats_len(d), dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", lib.sgf_attn_workspace_bytes(n, 1, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_bwd_reduce", _ptr(h), _ld(h), _ptr(g), _ld(g), _ptr(o), _ld(o),
-                      _ptr(den), n, d, _mm_code(h, "sgf_attn_h_supported", d), _ptr(hstats), _ptr(ws), ws.numel(), _stream(dev))
+        scratch = _scratch(dev, "attn", lib.sgf_attn_workspace_bytes(n, 1, d))
+        _launch(dev, "sgf_attn_h_bwd_reduce", h, _ld(h), g, _ld(g), o, _ld(o), den, n, d,
+                _mm_code(h, "sgf_attn_h_supported", d), hstats, *scratch)
         return hstats
 
     @staticmethod
@@ -708,17 +700,14 @@ class HipKernels:
         dh = torch.empty((n, d), dtype=h.dtype, device=dev)
         code = _mm_code(h, "sgf_attn_h_supported", d)
         nb = _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, code)
-        ws = _workspace(dev, "attn_h_part", nb) if nb else None
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_bwd_apply", _ptr(h), _ld(h), _ptr(g), _ld(g), _ptr(o), _ld(o),
-                      _ptr(den), n, d, code, _ptr(M), _ptr(w), _ptr(D), _ptr(ds), _ptr(dh),
-                      dh.stride(0), _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev))
+        _launch(dev, "sgf_attn_h_bwd_apply", h, _ld(h), g, _ld(g), o, _ld(o), den, n, d, code, M, w, D, ds, dh, dh.stride(0),
+                *(_scratch(dev, "attn_h_part", nb) if nb else _NO_SCRATCH))
         return dh
 
     @staticmethod
     def attn_h_bwd_split_supported(h, g, o) -> bool:
         d = h.shape[1]
-        return (h.dtype == _BF16 and bool(_lib.load().sgf_attn_h_bwd_split_supported(d, _lib.SGF_BF16))
+        return (h.dtype == _BF16 and bool(_lib.load().sgf_attn_h_bwd_split_supported(d, _code(h)))
                 and all(t.stride(-1) == 1 and (t.stride(0) * 2) % 16 == 0 and t.data_ptr() % 16 == 0 for t in (h, g, o)))
 
     @staticmethod
@@ -726,11 +715,9 @@ class HipKernels:
         """First apply pass of the backward (dnum M^T + dden w -> scratch) + the per-row scalars (1/den, dden)."""
         n, d = g.shape
         dev = g.device
-        ws = _workspace(dev, "attn_h_part", _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, _code(g)))
+        scratch = _scratch(dev, "attn_h_part", _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, _code(g)))
         rowscal = torch.empty((n, 2), dtype=_F32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_bwd_pre", _ptr(g), _ld(g), _ptr(o), _ld(o), _ptr(den), n, d, _code(g), _ptr(M),
-                      _ptr(w), _ptr(ws), ws.numel(), _ptr(rowscal), _stream(dev))
+        _launch(dev, "sgf_attn_h_bwd_pre", g, _ld(g), o, _ld(o), den, n, d, _code(g), M, w, *scratch, rowscal)
         return rowscal
 
     @staticmethod
@@ -739,10 +726,8 @@ class HipKernels:
         dev = h.device
         lib = _lib.load()
         hstats = torch.empty(lib.sgf_attn_h_bstats_len(d), dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", lib.sgf_attn_workspace_bytes(n, 1, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_bwd_reduce_scaled", _ptr(h), _ld(h), _ptr(g), _ld(g), _ptr(rowscal), n, d, _code(h),
-                      _ptr(hstats), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_attn_h_bwd_reduce_scaled", h, _ld(h), g, _ld(g), rowscal, n, d, _code(h), hstats,
+                *_scratch(dev, "attn", lib.sgf_attn_workspace_bytes(n, 1, d)))
         return hstats
 
     @staticmethod
@@ -750,11 +735,9 @@ class HipKernels:
         """dh = h D + ds + the scratch attn_h_bwd_pre left on this stream [+ addend, a second gradient of h]."""
         n, d = h.shape
         dev = h.device
-        ws = _workspace(dev, "attn_h_part", _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, _code(h)))
+        scratch = _scratch(dev, "attn_h_part", _lib.load().sgf_attn_h_bwd_apply_workspace_bytes(n, d, _code(h)))
         dh = torch.empty((n, d), dtype=h.dtype, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_attn_h_bwd_post", _ptr(h), _ld(h), n, d, _code(h), _ptr(D), _ptr(ds), _ptr(ws), ws.numel(),
-                      _ptr(addend), 0 if addend is None else _ld(addend), _ptr(dh), dh.stride(0), _stream(dev))
+        _launch(dev, "sgf_attn_h_bwd_post", h, _ld(h), n, d, _code(h), D, ds, *scratch, addend, _ld(addend), dh, dh.stride(0))
         return dh
 
     # ---- T4: dW = a^T b, db = colsum(a) ----
@@ -767,10 +750,8 @@ class HipKernels:
         if out is None:
             out = torch.empty((m, k), dtype=_F32, device=dev)
         cs = torch.empty(m, dtype=_F32, device=dev) if want_colsum else None
-        ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gram", _ptr(a), _ld(a), m, _ptr(b), _ld(b), k, n, _mm_code(a), _ptr(out),
-                      out.stride(0), _ptr(cs), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gram", a, _ld(a), m, b, _ld(b), k, n, _mm_code(a), out, out.stride(0), cs,
+                *_scratch(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k)))
         return out, cs
 
     @staticmethod
@@ -780,10 +761,8 @@ class HipKernels:
         k = b1.shape[1]
         dev = a.device
         cs = torch.empty(m, dtype=_F32, device=dev) if want_colsum else None
-        ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gram2", _ptr(a), _ld(a), m, _ptr(b1), _ld(b1), _ptr(b2), _ld(b2), k, n, _mm_code(a), _ptr(out1),
-                      out1.stride(0), _ptr(out2), out2.stride(0), _ptr(cs), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gram2", a, _ld(a), m, b1, _ld(b1), b2, _ld(b2), k, n, _mm_code(a), out1, out1.stride(0), out2,
+                out2.stride(0), cs, *_scratch(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k)))
         return cs
 
     # ---- T5 ----
@@ -794,10 +773,8 @@ class HipKernels:
         y = torch.empty((n, d), dtype=x.dtype, device=dev)
         mean = torch.empty(n, dtype=_F32, device=dev) if gamma is not None else None
         rstd = torch.empty(n, dtype=_F32, device=dev) if gamma is not None else None
-        with torch.cuda.device(dev):
-            _lib.call("sgf_ln_fwd", _ptr(x), _ld(x), _ptr(res), _ld(res), float(a), float(b),
-                      _ptr(gamma), _ptr(beta), int(relu), float(eps), n, d, _code(x), _ptr(y),
-                      y.stride(0), _ptr(mean), _ptr(rstd), _stream(dev))
+        _launch(dev, "sgf_ln_fwd", x, _ld(x), res, _ld(res), float(a), float(b), gamma, beta, int(relu), float(eps), n, d,
+                _code(x), y, y.stride(0), mean, rstd)
         return y, mean, rstd
 
     @staticmethod
@@ -811,12 +788,9 @@ class HipKernels:
         dres = torch.empty_like(res) if (res is not None and not shared) else None
         dgamma = torch.empty(d, dtype=_F32, device=dev) if gamma is not None else None
         dbeta = torch.empty(d, dtype=_F32, device=dev) if gamma is not None else None
-        ws = _workspace(dev, "ln", _lib.load().sgf_ln_bwd_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_ln_bwd", _ptr(gy), _ld(gy), _ptr(y), _ld(y), _ptr(x), _ld(x), _ptr(res),
-                      _ld(res), float(a), float(b), _ptr(gamma), int(relu), _ptr(mean), _ptr(rstd), n,
-                      d, _code(x), _ptr(dx), _ld(dx), _ptr(dres), _ld(dres), _ptr(dgamma), _ptr(dbeta),
-                      _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_ln_bwd", gy, _ld(gy), y, _ld(y), x, _ld(x), res, _ld(res), float(a), float(b), gamma, int(relu), mean,
+                rstd, n, d, _code(x), dx, _ld(dx), dres, _ld(dres), dgamma, dbeta,
+                *_scratch(dev, "ln", _lib.load().sgf_ln_bwd_workspace_bytes(n, d)))
         return dx, (dx if shared else dres), dgamma, dbeta
 
     # ---- T6 ----
@@ -825,10 +799,8 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         stats = torch.empty(2 * d, dtype=_F32, device=dev)
-        ws = _workspace(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_colstats", _ptr(x), _ld(x), _ptr(shift), n, d, _code(x), _ptr(stats),
-                      _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_colstats", x, _ld(x), shift, n, d, _code(x), stats,
+                *_scratch(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d)))
         return stats
 
     @staticmethod
@@ -837,9 +809,8 @@ class HipKernels:
         d = sums.numel() // 2
         mean = torch.empty(d, dtype=_F32, device=sums.device)
         rstd = torch.empty(d, dtype=_F32, device=sums.device)
-        with torch.cuda.device(sums.device):
-            _lib.call("sgf_bn_finalize", _ptr(sums), _ptr(shift), float(n_total), float(eps), float(momentum),
-                      _ptr(running_mean), _ptr(running_var), d, _ptr(mean), _ptr(rstd), _stream(sums.device))
+        _launch(sums.device, "sgf_bn_finalize", sums, shift, float(n_total), float(eps), float(momentum), running_mean,
+                running_var, d, mean, rstd)
         return mean, rstd
 
     @staticmethod
@@ -847,10 +818,7 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         y = torch.empty((n, d), dtype=x.dtype, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_bn_apply", _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
-                      _ptr(res), _ld(res), int(relu), n, d, _code(x), _ptr(y), y.stride(0),
-                      _stream(dev))
+        _launch(dev, "sgf_bn_apply", x, _ld(x), mean, rstd, gamma, beta, res, _ld(res), int(relu), n, d, _code(x), y, y.stride(0))
         return y
 
     @staticmethod
@@ -862,10 +830,8 @@ class HipKernels:
         nbytes = _lib.load().sgf_spmm_packed_bytes(n, int(slot_bytes))
         packed = PackedRows(torch.empty(nbytes, dtype=torch.uint8, device=dev), int(slot_bytes), n,
                             torch.empty(1, dtype=torch.int32, device=dev))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_bn_apply_packed", _ptr(x), _ld(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
-                      _ptr(res), _ld(res), int(relu), n, d, _code(x), _ptr(y), y.stride(0), _ptr(packed.slots),
-                      packed.slot_bytes, _ptr(packed.overflow), _stream(dev))
+        _launch(dev, "sgf_bn_apply_packed", x, _ld(x), mean, rstd, gamma, beta, res, _ld(res), int(relu), n, d, _code(x), y,
+                y.stride(0), packed.slots, packed.slot_bytes, packed.overflow)
         return y, packed
 
     @staticmethod
@@ -873,11 +839,8 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         stats = torch.empty(2 * d, dtype=_F32, device=dev)
-        ws = _workspace(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_bn_bwd_stats", _ptr(gy), _ld(gy), _ptr(x), _ld(x), _ptr(mean), _ptr(rstd),
-                      _ptr(gamma), _ptr(beta), int(relu), n, d, _code(x), _ptr(stats), _ptr(ws),
-                      ws.numel(), _stream(dev))
+        _launch(dev, "sgf_bn_bwd_stats", gy, _ld(gy), x, _ld(x), mean, rstd, gamma, beta, int(relu), n, d, _code(x), stats,
+                *_scratch(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d)))
         return stats
 
     @staticmethod
@@ -886,15 +849,13 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         stats = torch.empty(2 * d, dtype=_F32, device=dev)
-        ws = _workspace(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_bn_bwd_stats2", _ptr(gy), _ld(gy), _ptr(gy2), _ld(gy2), _ptr(x), _ld(x), _ptr(mean), _ptr(rstd),
-                      _ptr(gamma), _ptr(beta), int(relu), n, d, _code(x), _ptr(stats), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_bn_bwd_stats2", gy, _ld(gy), gy2, _ld(gy2), x, _ld(x), mean, rstd, gamma, beta, int(relu), n, d,
+                _code(x), stats, *_scratch(dev, "col", _lib.load().sgf_colstats_workspace_bytes(n, d)))
         return stats
 
     @staticmethod
     def gram_ln_bwd_supported(m: int, k: int, dtype) -> bool:
-        return dtype == _BF16 and bool(_lib.load().sgf_gram_ln_bwd_supported(int(m), int(k), _lib.SGF_BF16))
+        return dtype == _BF16 and bool(_lib.load().sgf_gram_ln_bwd_supported(int(m), int(k), _dtype_code(dtype)))
 
     @staticmethod
     def gram_ln_bwd(g, xin, mean, rstd, gamma, beta, relu: bool, b):
@@ -906,16 +867,13 @@ class HipKernels:
         cs = torch.empty(m, dtype=_F32, device=dev)
         dg = torch.empty(m, dtype=_F32, device=dev)
         db = torch.empty(m, dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gram_ln_bwd", _ptr(g), _ld(g), _ptr(xin), _ld(xin), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
-                      int(relu), m, _ptr(b), _ld(b), k, n, _code(xin), _ptr(out), out.stride(0), _ptr(cs), _ptr(dg), _ptr(db),
-                      _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gram_ln_bwd", g, _ld(g), xin, _ld(xin), mean, rstd, gamma, beta, int(relu), m, b, _ld(b), k, n,
+                _code(xin), out, out.stride(0), cs, dg, db, *_scratch(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k)))
         return out, cs, dg, db
 
     @staticmethod
     def gram_bn_bwd_supported(m: int, k: int, dtype) -> bool:
-        return dtype == _BF16 and bool(_lib.load().sgf_gram_bn_bwd_supported(int(m), int(k), _lib.SGF_BF16))
+        return dtype == _BF16 and bool(_lib.load().sgf_gram_bn_bwd_supported(int(m), int(k), _dtype_code(dtype)))
 
     @staticmethod
     def gram_bn_bwd(gy, gy2, z, mean, rstd, gamma, beta, relu: bool, stats, inv_n: float, training: bool, b):
@@ -925,11 +883,9 @@ class HipKernels:
         dev = z.device
         out = torch.empty((m, k), dtype=_F32, device=dev)
         cs = torch.empty(m, dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gram_bn_bwd", _ptr(gy), _ld(gy), _ptr(gy2), _ld(gy2), _ptr(z), _ld(z), _ptr(mean), _ptr(rstd),
-                      _ptr(gamma), _ptr(beta), int(relu), _ptr(stats), float(inv_n), int(training), m, _ptr(b), _ld(b), k, n,
-                      _code(z), _ptr(out), out.stride(0), _ptr(cs), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gram_bn_bwd", gy, _ld(gy), gy2, _ld(gy2), z, _ld(z), mean, rstd, gamma, beta, int(relu), stats,
+                float(inv_n), int(training), m, b, _ld(b), k, n, _code(z), out, out.stride(0), cs,
+                *_scratch(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k)))
         return out, cs
 
     @staticmethod
@@ -939,7 +895,7 @@ class HipKernels:
         ok = all(t.dtype == _BF16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
                  for t in (g, z, b1, b2))
         return (ok and b1.shape == b2.shape and g.shape == z.shape
-                and bool(_lib.load().sgf_gram2_bn_bwd_supported(int(m), int(b1.shape[1]), int(n), _lib.SGF_BF16)))
+                and bool(_lib.load().sgf_gram2_bn_bwd_supported(int(m), int(b1.shape[1]), int(n), _code(z))))
 
     @staticmethod
     def gram2_bn_bwd(g, z, mean, rstd, gamma, beta, relu: bool, stats, inv_n: float, training: bool, b1, b2, out1, out2):
@@ -950,12 +906,9 @@ class HipKernels:
         dev = z.device
         dz = torch.empty((n, m), dtype=z.dtype, device=dev)
         cs = torch.empty(m, dtype=_F32, device=dev)
-        ws = _workspace(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gram2_bn_bwd", _ptr(g), _ld(g), _ptr(z), _ld(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
-                      int(relu), _ptr(stats), float(inv_n), int(training), m, _ptr(b1), _ld(b1), _ptr(b2), _ld(b2), k, n,
-                      _code(z), _ptr(dz), dz.stride(0), _ptr(out1), out1.stride(0), _ptr(out2), out2.stride(0), _ptr(cs),
-                      _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gram2_bn_bwd", g, _ld(g), z, _ld(z), mean, rstd, gamma, beta, int(relu), stats, float(inv_n),
+                int(training), m, b1, _ld(b1), b2, _ld(b2), k, n, _code(z), dz, dz.stride(0), out1, out1.stride(0), out2,
+                out2.stride(0), cs, *_scratch(dev, "attn", _lib.load().sgf_gram_workspace_bytes(n, m, k)))
         return dz, cs
 
     @staticmethod
@@ -964,10 +917,8 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         dx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_bn_bwd_apply", _ptr(gy), _ld(gy), _ptr(x), _ld(x), _ptr(mean), _ptr(rstd),
-                      _ptr(gamma), _ptr(beta), int(relu), _ptr(stats), float(inv_n), int(training), n,
-                      d, _code(x), _ptr(dx), _ld(dx), _stream(dev))
+        _launch(dev, "sgf_bn_bwd_apply", gy, _ld(gy), x, _ld(x), mean, rstd, gamma, beta, int(relu), stats, float(inv_n),
+                int(training), n, d, _code(x), dx, _ld(dx))
         return dx
 
     @staticmethod
@@ -975,10 +926,8 @@ class HipKernels:
         n, d = x.shape
         dev = x.device
         out = torch.empty(d, dtype=_F32, device=dev)
-        ws = _workspace(dev, "colsum", _lib.load().sgf_colsum_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_colsum", _ptr(x), _ld(x), n, d, _code(x), _ptr(out), _ptr(ws), ws.numel(),
-                      _stream(dev))
+        _launch(dev, "sgf_colsum", x, _ld(x), n, d, _code(x), out,
+                *_scratch(dev, "colsum", _lib.load().sgf_colsum_workspace_bytes(n, d)))
         return out
 
     # ---- dropout (+ residual), mask recomputed from the seed ----
@@ -986,9 +935,7 @@ class HipKernels:
     def dropout(x, res, p: float, seed: int) -> torch.Tensor:
         n, d = x.shape
         y = torch.empty((n, d), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("sgf_dropout", _ptr(x), _ld(x), _ptr(res), _ld(res), float(p), int(seed), n, d,
-                      _code(x), _ptr(y), y.stride(0), _stream(x.device))
+        _launch(x.device, "sgf_dropout", x, _ld(x), res, _ld(res), float(p), int(seed), n, d, _code(x), y, y.stride(0))
         return y
 
     @staticmethod
@@ -1000,9 +947,8 @@ class HipKernels:
             raise IndexError(f"dropout_dev: slot {slot} outside a bank of {seeds.numel()}")
         n, d = x.shape
         y = torch.empty((n, d), dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("sgf_dropout_dev", _ptr(x), _ld(x), _ptr(res), _ld(res), float(p), seeds.data_ptr() + 8 * int(slot),
-                      n, d, _code(x), _ptr(y), y.stride(0), _stream(x.device))
+        _launch(x.device, "sgf_dropout_dev", x, _ld(x), res, _ld(res), float(p), seeds.data_ptr() + 8 * int(slot), n, d,
+                _code(x), y, y.stride(0))
         return y
 
     # ---- N4: log_softmax + NLL on the training rows ----
@@ -1011,10 +957,8 @@ class HipKernels:
         n, c = logits.shape
         dev = logits.device
         out = torch.empty(1, dtype=_F32, device=dev)
-        ws = _workspace(dev, "nll", _lib.load().sgf_nll_workspace_bytes(idx.numel()))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_nll_fwd", _ptr(logits), logits.stride(0), n, c, _code(logits), _ptr(labels),
-                      _ptr(idx), idx.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_nll_fwd", logits, logits.stride(0), n, c, _code(logits), labels, idx, idx.numel(), out,
+                *_scratch(dev, "nll", _lib.load().sgf_nll_workspace_bytes(idx.numel())))
         return out
 
     @staticmethod
@@ -1022,16 +966,13 @@ class HipKernels:
         n, c = logits.shape
         dev = logits.device
         d = torch.empty((n, c), dtype=logits.dtype, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("sgf_nll_bwd", _ptr(logits), logits.stride(0), n, c, _code(logits), _ptr(labels),
-                      _ptr(idx), idx.numel(), _ptr(gout), float(inv_denom), _ptr(d), d.stride(0),
-                      _stream(dev))
+        _launch(dev, "sgf_nll_bwd", logits, logits.stride(0), n, c, _code(logits), labels, idx, idx.numel(), gout,
+                float(inv_denom), d, d.stride(0))
         return d
 
     # ---- N4b: BCEWithLogitsLoss on the training rows (idx None: the dense form, every row) ----
-    # These two sit on a path whose GPU work is a few microseconds at mini-batch sizes: the host side is kept to one pass
-    # over the arguments, one allocation and one ctypes call each (constant workspace size cached, no device context
-    # switch when the tensors' device is already current).
+    # These two sit on a path whose GPU work is a few microseconds at mini-batch sizes: one pass over the arguments and one
+    # allocation each on top of what _launch does.
     @staticmethod
     def _bce_args(logits, target, idx):
         """(n, c, m, target, kind, ldt) after the checks both entries share: logits [n, c] fp32 / bf16 with unit inner stride
@@ -1065,8 +1006,6 @@ class HipKernels:
                 raise ValueError(f"bce: idx holds {m} rows of a {n}-row matrix (rows must be distinct)")
         return n, c, m, target, kind, ldt
 
-    _bce_ws_bytes = None
-
     @staticmethod
     def bce_fwd(logits, target, idx, inv_denom: float = 1.0) -> torch.Tensor:
         """inv_denom * sum of the element losses over the rows idx, as a 0-dim fp32 tensor."""
@@ -1074,16 +1013,8 @@ class HipKernels:
         dev = logits.device
         code = _code(logits)
         out = torch.empty((), dtype=_F32, device=dev)
-        if HipKernels._bce_ws_bytes is None:       # (a constant of the library: the block-partial buffer)
-            HipKernels._bce_ws_bytes = int(_lib.load().sgf_bce_workspace_bytes(m, c))
-        ws = _workspace(dev, "bce", HipKernels._bce_ws_bytes)
-        args = (_ptr(logits), max(logits.stride(0), c), n, c, code, _ptr(target), ldt, kind, _ptr(idx), m, float(inv_denom),
-                _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        if torch.cuda.current_device() == dev.index:
-            _lib.call("sgf_bce_fwd", *args)
-        else:
-            with torch.cuda.device(dev):
-                _lib.call("sgf_bce_fwd", *args)
+        _launch(dev, "sgf_bce_fwd", logits, max(logits.stride(0), c), n, c, code, target, ldt, kind, idx, m, float(inv_denom),
+                out, *_scratch(dev, "bce", _const_bytes("sgf_bce_workspace_bytes", m, c)))
         return out
 
     @staticmethod
@@ -1093,13 +1024,8 @@ class HipKernels:
         if gout.dtype != _F32 or gout.numel() != 1 or gout.device != dev:
             raise ValueError("bce: gout must be one float32 on the logits' device")
         d = torch.empty((n, c), dtype=logits.dtype, device=dev)
-        args = (_ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(target), ldt, kind, _ptr(idx), m,
-                _ptr(gout), float(inv_denom), _ptr(d), c, _stream(dev))
-        if torch.cuda.current_device() == dev.index:
-            _lib.call("sgf_bce_bwd", *args)
-        else:
-            with torch.cuda.device(dev):
-                _lib.call("sgf_bce_bwd", *args)
+        _launch(dev, "sgf_bce_bwd", logits, max(logits.stride(0), c), n, c, _code(logits), target, ldt, kind, idx, m, gout,
+                float(inv_denom), d, c)
         return d
 
     # ---- N5: the evaluation metrics as integer counts (idx None: every row) ----
@@ -1150,18 +1076,14 @@ class HipKernels:
         n, c, m, target, kind, ldt = HipKernels._metric_args("rocauc_counts", logits, target, idx, True)
         dev = logits.device
         counts = torch.empty((c, 6), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            nbytes = int(_lib.load().sgf_rocauc_workspace_bytes(m, c)) if m else 0
-            if m and c >= 1 and nbytes == 0:
-                _lib.check(_lib.SGF_E_HIP if hasattr(_lib, "SGF_E_HIP") else -3, "sgf_rocauc_workspace_bytes")
-            # some 24 m c bytes (230 MB at the ogbn-proteins train split) for a call made once every eval_step epochs:
-            # taken from the caching allocator and given back, not kept in the per-stream scratch cache
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-            _lib.call("sgf_rocauc_counts", _ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(target), ldt, kind,
-                      _ptr(idx), m, _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+        nbytes = int(_lib.load().sgf_rocauc_workspace_bytes(m, c)) if m else 0
+        if m and c >= 1 and nbytes == 0:
+            _lib.check(_lib.SGF_E_HIP, "sgf_rocauc_workspace_bytes")
+        # some 24 m c bytes (230 MB at the ogbn-proteins train split) for a call made once every eval_step epochs:
+        # taken from the caching allocator and given back, not kept in the per-stream scratch cache
+        _launch(dev, "sgf_rocauc_counts", logits, max(logits.stride(0), c), n, c, _code(logits), target, ldt, kind, idx, m,
+                counts, *_scratch(dev, None, nbytes))
         return counts
-
-    _argmax_ws_bytes = None
 
     @staticmethod
     def argmax_count(logits, labels, idx) -> torch.Tensor:
@@ -1169,12 +1091,8 @@ class HipKernels:
         n, c, m, labels, kind, stride = HipKernels._metric_args("argmax_count", logits, labels, idx, False)
         dev = logits.device
         counts = torch.empty((2,), dtype=torch.int64, device=dev)
-        if HipKernels._argmax_ws_bytes is None:    # (a constant of the library: the block-partial buffer)
-            HipKernels._argmax_ws_bytes = int(_lib.load().sgf_argmax_workspace_bytes(m, c))
-        with torch.cuda.device(dev):
-            ws = _workspace(dev, "argmax", HipKernels._argmax_ws_bytes)
-            _lib.call("sgf_argmax_count", _ptr(logits), max(logits.stride(0), c), n, c, _code(logits), _ptr(labels), stride,
-                      kind, _ptr(idx), m, _ptr(counts), _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_argmax_count", logits, max(logits.stride(0), c), n, c, _code(logits), labels, stride, kind, idx, m,
+                counts, *_scratch(dev, "argmax", _const_bytes("sgf_argmax_workspace_bytes", m, c)))
         return counts
 
     @staticmethod
@@ -1186,8 +1104,7 @@ class HipKernels:
         k = len(xs)
         ptrs = (ctypes.c_void_p * k)(*[x.data_ptr() for x in xs])
         lds = (ctypes.c_int64 * k)(*[x.stride(0) for x in xs])
-        with torch.cuda.device(y.device):
-            _lib.call("sgf_sum_n", ptrs, lds, k, n, d, _code(y), _ptr(y), y.stride(0), _stream(y.device))
+        _launch(y.device, "sgf_sum_n", ptrs, lds, k, n, d, _code(y), y, y.stride(0))
         return y
 
     # ---- T7 fused: logits = (a x1 + b x2) W^T + bias ----
@@ -1195,16 +1112,17 @@ class HipKernels:
     def combine_fc_supported(d: int, classes: int, dtype) -> bool:
         """bf16: d % 32 == 0, d <= 256, classes <= 64 (csrc/head.hip); fp32: d % 4 == 0, d <= 256 and the class count
         PADDED to a multiple of 4 (ops.combine_fc pads W / bias with zero rows) up to 256 (csrc/linear_f32.hip)."""
-        if dtype == _F32:
-            return bool(_lib.load().sgf_combine_fc_supported(d, (classes + 3) // 4 * 4, _lib.SGF_F32))
-        if dtype == _BF16 and classes > 64:      # the same exact-fp32 kernel with bf16 rows on the wire (C = 172: papers100M)
-            return bool(_lib.load().sgf_combine_fc_supported(d, (classes + 3) // 4 * 4, _lib.SGF_BF16))
-        return dtype == _BF16 and bool(_lib.load().sgf_combine_fc_supported(d, classes, _lib.SGF_BF16))
+        if dtype not in (_F32, _BF16):
+            return False
+        # bf16 with more than 64 classes: the same exact-fp32 kernel with bf16 rows on the wire (C = 172: papers100M)
+        if dtype == _F32 or classes > 64:
+            classes = (classes + 3) // 4 * 4
+        return bool(_lib.load().sgf_combine_fc_supported(d, classes, _dtype_code(dtype)))
 
     @staticmethod
     def combine_fc_mapped_supported(d: int, classes: int, dtype) -> bool:
         """the row-mapped forms (sgf_combine_fc_*_mapped): the bf16 kernels of csrc/head.hip only"""
-        return dtype == _BF16 and classes <= 64 and bool(_lib.load().sgf_combine_fc_supported(d, classes, _lib.SGF_BF16))
+        return dtype == _BF16 and classes <= 64 and bool(_lib.load().sgf_combine_fc_supported(d, classes, _dtype_code(dtype)))
 
     @staticmethod
     def combine_fc_fwd(x1, a: float, x2, b: float, w, bias, row_map=None) -> torch.Tensor:
@@ -1213,14 +1131,12 @@ class HipKernels:
         c = w.shape[0]
         HipKernels._check_row_map(row_map, n, x1.device)
         logits = torch.empty((n, c), dtype=_F32, device=x1.device)
-        with torch.cuda.device(x1.device):
-            if row_map is None:
-                _lib.call("sgf_combine_fc_fwd", _ptr(x1), _ld(x1), float(a), _ptr(x2), _ld(x2), float(b), _ptr(w),
-                          _ptr(bias), n, d, c, _mm_code(x1, "sgf_combine_fc_supported", d, c), _ptr(logits),
-                          logits.stride(0), _stream(x1.device))
-            else:
-                _lib.call("sgf_combine_fc_fwd_mapped", _ptr(x1), _ld(x1), float(a), _ptr(x2), _ld(x2), float(b), _ptr(w),
-                          _ptr(bias), n, d, c, _code(x1), _ptr(logits), logits.stride(0), _ptr(row_map), _stream(x1.device))
+        if row_map is None:
+            _launch(x1.device, "sgf_combine_fc_fwd", x1, _ld(x1), float(a), x2, _ld(x2), float(b), w, bias, n, d, c,
+                    _mm_code(x1, "sgf_combine_fc_supported", d, c), logits, logits.stride(0))
+        else:
+            _launch(x1.device, "sgf_combine_fc_fwd_mapped", x1, _ld(x1), float(a), x2, _ld(x2), float(b), w, bias, n, d, c,
+                    _code(x1), logits, logits.stride(0), row_map)
         return logits
 
     @staticmethod
@@ -1231,15 +1147,12 @@ class HipKernels:
         HipKernels._check_row_map(row_map, n, g.device)
         dx1 = torch.empty((n, d), dtype=dtype, device=g.device)
         dx2 = torch.empty((n, d), dtype=dtype, device=g.device)
-        with torch.cuda.device(g.device):
-            if row_map is None:
-                _lib.call("sgf_combine_fc_bwd", _ptr(g), g.stride(0), _ptr(w), n, d, c, float(a), float(b),
-                          _mm_code(dx1, "sgf_combine_fc_supported", d, c), _ptr(dx1), dx1.stride(0), _ptr(dx2),
-                          dx2.stride(0), _stream(g.device))
-            else:
-                _lib.call("sgf_combine_fc_bwd_mapped", _ptr(g), g.stride(0), _ptr(w), n, d, c, float(a), float(b),
-                          _lib.SGF_BF16, _ptr(dx1), dx1.stride(0), _ptr(dx2), dx2.stride(0), _ptr(row_map),
-                          _stream(g.device))
+        if row_map is None:
+            _launch(g.device, "sgf_combine_fc_bwd", g, g.stride(0), w, n, d, c, float(a), float(b),
+                    _mm_code(dx1, "sgf_combine_fc_supported", d, c), dx1, dx1.stride(0), dx2, dx2.stride(0))
+        else:
+            _launch(g.device, "sgf_combine_fc_bwd_mapped", g, g.stride(0), w, n, d, c, float(a), float(b), _lib.SGF_BF16, dx1,
+                    dx1.stride(0), dx2, dx2.stride(0), row_map)
         return dx1, dx2
 
     @staticmethod
@@ -1252,9 +1165,8 @@ class HipKernels:
         dx1 = torch.empty((n, d), dtype=_BF16, device=g.device)
         dx2 = torch.empty((n, d), dtype=_BF16, device=g.device)
         gp = torch.empty((n, (c + 15) // 16 * 16), dtype=_BF16, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.call("sgf_combine_fc_bwd_g", _ptr(g), g.stride(0), _ptr(w), n, d, c, float(a), float(b), _lib.SGF_BF16, _ptr(dx1),
-                      dx1.stride(0), _ptr(dx2), dx2.stride(0), _ptr(row_map), _ptr(gp), gp.stride(0), _stream(g.device))
+        _launch(g.device, "sgf_combine_fc_bwd_g", g, g.stride(0), w, n, d, c, float(a), float(b), _code(dx1), dx1, dx1.stride(0),
+                dx2, dx2.stride(0), row_map, gp, gp.stride(0))
         return dx1, dx2, gp
 
     @staticmethod
@@ -1270,9 +1182,7 @@ class HipKernels:
     def gcn_epilogue_supported(d_in: int, d_out: int, dtype) -> bool:
         """bf16 storage: square layers of 64 / 128 / 256 (csrc/rowgemm.hip); fp32 storage: any widths % 4 == 0 up to
         256 (csrc/linear_f32.hip, exact-fp32 matrix cores)."""
-        if dtype not in (_BF16, _F32):
-            return False
-        return bool(_lib.load().sgf_gcn_epilogue_supported(d_in, d_out, _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+        return dtype in (_BF16, _F32) and bool(_lib.load().sgf_gcn_epilogue_supported(d_in, d_out, _dtype_code(dtype)))
 
     @staticmethod
     def gcn_epilogue_stats(a, w, bias, shift=None, want_stats=False):
@@ -1283,12 +1193,9 @@ class HipKernels:
         dev = a.device
         y = torch.empty((n, d_out), dtype=a.dtype, device=dev)
         stats = torch.empty(2 * d_out, dtype=_F32, device=dev) if want_stats else None
-        lib = _lib.load()
-        ws = _workspace(dev, "gcn_epi", lib.sgf_gcn_epilogue_workspace_bytes(n, d_out)) if want_stats else None
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gcn_epilogue_stats", _ptr(a), _ld(a), _ptr(w), w.stride(0), _ptr(bias), n, d_in, d_out,
-                      _mm_code(a, "sgf_gcn_epilogue_supported", d_in, d_out), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
-                      0 if ws is None else ws.numel(), _stream(dev))
+        scratch = _stats_scratch(dev, n, d_out, want_stats)
+        _launch(dev, "sgf_gcn_epilogue_stats", a, _ld(a), w, w.stride(0), bias, n, d_in, d_out,
+                _mm_code(a, "sgf_gcn_epilogue_supported", d_in, d_out), y, _ld(y), shift, stats, *scratch)
         return y, stats
 
     @staticmethod
@@ -1301,32 +1208,25 @@ class HipKernels:
         d2, d = a2.shape[1], w.shape[0]
         dev = a1.device
         lib = _lib.load()
-        if (a1.dtype == _BF16 and d1 == d2 == d and _one_pass_cat() and lib.sgf_gcn_epilogue_cat_supported(d, _lib.SGF_BF16)
-                and w.stride(1) == 1 and w.shape[1] == 2 * d):
-            y = torch.empty((n, d), dtype=a1.dtype, device=dev)
-            stats = torch.empty(2 * d, dtype=_F32, device=dev) if want_stats else None
-            ws = _workspace(dev, "gcn_epi", lib.sgf_gcn_epilogue_workspace_bytes(n, d)) if want_stats else None
-            with torch.cuda.device(dev):
-                _lib.call("sgf_gcn_epilogue_cat", _ptr(a1), _ld(a1), _ptr(a2), _ld(a2), _ptr(w), w.stride(0), _ptr(bias), n,
-                          d, _code(a1), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
-                          0 if ws is None else ws.numel(), _stream(dev))
-            return y, stats
-        part = _workspace(dev, "gcn_part", lib.sgf_gcn_epilogue_dtype_partial_bytes(n, d, _code(a1)))
+        one_pass = (a1.dtype == _BF16 and d1 == d2 == d and _one_pass_cat() and lib.sgf_gcn_epilogue_cat_supported(d, _code(a1))
+                    and w.stride(1) == 1 and w.shape[1] == 2 * d)
+        part = None if one_pass else _scratch(dev, "gcn_part", lib.sgf_gcn_epilogue_dtype_partial_bytes(n, d, _code(a1)))
         y = torch.empty((n, d), dtype=a1.dtype, device=dev)
         stats = torch.empty(2 * d, dtype=_F32, device=dev) if want_stats else None
-        ws = _workspace(dev, "gcn_epi", lib.sgf_gcn_epilogue_workspace_bytes(n, d)) if want_stats else None
-        w1, w2 = w[:, :d1], w[:, d1:]
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gcn_epilogue_partial", _ptr(a1), _ld(a1), _ptr(w1), w.stride(0), _ptr(bias), n, d1, d,
-                      _mm_code(a1, "sgf_gcn_epilogue_supported", d1, d), _ptr(part), part.numel(), _stream(dev))
-            _lib.call("sgf_gcn_epilogue_stats_add", _ptr(a2), _ld(a2), _ptr(w2), w.stride(0), _ptr(part),
-                      part.numel(), n, d2, d, _mm_code(a2, "sgf_gcn_epilogue_supported", d2, d), _ptr(y), _ld(y), _ptr(shift), _ptr(stats), _ptr(ws),
-                      0 if ws is None else ws.numel(), _stream(dev))
+        scratch = _stats_scratch(dev, n, d, want_stats)
+        if one_pass:
+            _launch(dev, "sgf_gcn_epilogue_cat", a1, _ld(a1), a2, _ld(a2), w, w.stride(0), bias, n, d, _code(a1), y, _ld(y),
+                    shift, stats, *scratch)
+            return y, stats
+        _launch(dev, "sgf_gcn_epilogue_partial", a1, _ld(a1), w[:, :d1], w.stride(0), bias, n, d1, d,
+                _mm_code(a1, "sgf_gcn_epilogue_supported", d1, d), *part)
+        _launch(dev, "sgf_gcn_epilogue_stats_add", a2, _ld(a2), w[:, d1:], w.stride(0), *part, n, d2, d,
+                _mm_code(a2, "sgf_gcn_epilogue_supported", d2, d), y, _ld(y), shift, stats, *scratch)
         return y, stats
 
     @staticmethod
     def stem_pair_supported(d_in: int, d_out: int, dtype) -> bool:
-        return dtype == _BF16 and bool(_lib.load().sgf_stem_pair_supported(d_in, d_out, _lib.SGF_BF16))
+        return dtype == _BF16 and bool(_lib.load().sgf_stem_pair_supported(d_in, d_out, _dtype_code(dtype)))
 
     @staticmethod
     def stem_pair(x, w0, b0, w1, b1, shift0=None, want_stats0=False):
@@ -1337,13 +1237,8 @@ class HipKernels:
         y0 = torch.empty((n, d_out), dtype=x.dtype, device=dev)
         y1 = torch.empty((n, d_out), dtype=x.dtype, device=dev) if w1 is not None else None
         stats = torch.empty(2 * d_out, dtype=_F32, device=dev) if want_stats0 else None
-        lib = _lib.load()
-        ws = _workspace(dev, "gcn_epi", lib.sgf_gcn_epilogue_workspace_bytes(n, d_out)) if want_stats0 else None
-        with torch.cuda.device(dev):
-            _lib.call("sgf_stem_pair", _ptr(x), _ld(x), n, d_in, _ptr(w0), w0.stride(0), _ptr(b0), _ptr(w1),
-                      0 if w1 is None else w1.stride(0), _ptr(b1), d_out, _code(x), _ptr(y0), _ld(y0), _ptr(y1),
-                      0 if y1 is None else _ld(y1), _ptr(shift0), _ptr(stats), _ptr(ws), 0 if ws is None else ws.numel(),
-                      _stream(dev))
+        _launch(dev, "sgf_stem_pair", x, _ld(x), n, d_in, w0, w0.stride(0), b0, w1, _ld(w1), b1, d_out, _code(x), y0, _ld(y0), y1,
+                _ld(y1), shift0, stats, *_stats_scratch(dev, n, d_out, want_stats0))
         return y0, y1, stats
 
     @staticmethod
@@ -1352,15 +1247,13 @@ class HipKernels:
         n, d_out = dy.shape
         d_in = w.shape[1]
         dx = torch.empty((n, d_in), dtype=dy.dtype, device=dy.device)
-        with torch.cuda.device(dy.device):
-            _lib.call("sgf_gcn_epilogue_dx", _ptr(dy), _ld(dy), _ptr(w), w.stride(0), n, d_in, d_out,
-                      _mm_code(dy, "sgf_gcn_epilogue_supported", d_out, d_in),
-                      _ptr(dx), _ld(dx), _stream(dy.device))
+        _launch(dy.device, "sgf_gcn_epilogue_dx", dy, _ld(dy), w, w.stride(0), n, d_in, d_out,
+                _mm_code(dy, "sgf_gcn_epilogue_supported", d_out, d_in), dx, _ld(dx))
         return dx
 
     @staticmethod
     def gcn_epilogue_dx2_acc_supported(d: int, dtype) -> bool:
-        return dtype == _BF16 and bool(_lib.load().sgf_gcn_epilogue_dx2_acc_supported(int(d), _lib.SGF_BF16))
+        return dtype == _BF16 and bool(_lib.load().sgf_gcn_epilogue_dx2_acc_supported(int(d), _dtype_code(dtype)))
 
     @staticmethod
     def gcn_epilogue_dx2_acc(dz, w, gadd, acc_in):
@@ -1369,14 +1262,13 @@ class HipKernels:
         n, d = dz.shape
         dy = torch.empty_like(dz)
         acc = torch.empty_like(dz)
-        with torch.cuda.device(dz.device):
-            _lib.call("sgf_gcn_epilogue_dx2_acc", _ptr(dz), _ld(dz), _ptr(w), _ld(w), n, d, _code(dz), _ptr(dy), _ld(dy),
-                      _ptr(gadd), _ld(gadd), _ptr(acc_in), _ld(acc_in), _ptr(acc), _ld(acc), _stream(dz.device))
+        _launch(dz.device, "sgf_gcn_epilogue_dx2_acc", dz, _ld(dz), w, _ld(w), n, d, _code(dz), dy, _ld(dy), gadd, _ld(gadd),
+                acc_in, _ld(acc_in), acc, _ld(acc))
         return dy, acc
 
     @staticmethod
     def gcn_bn_bwd_dx_supported(d: int, dtype) -> bool:
-        return dtype == _BF16 and bool(_lib.load().sgf_gcn_bn_bwd_dx_supported(int(d), _lib.SGF_BF16))
+        return dtype == _BF16 and bool(_lib.load().sgf_gcn_bn_bwd_dx_supported(int(d), _dtype_code(dtype)))
 
     @staticmethod
     def gcn_bn_bwd_dx(gy, z, mean, rstd, gamma, beta, relu: bool, stats, inv_n: float, training: bool, w, acc_in,
@@ -1391,12 +1283,9 @@ class HipKernels:
         nbytes = _lib.load().sgf_gcn_epilogue_partial_bytes(n, d)
         acc_out = None if last else torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         dx0 = torch.empty((n, d), dtype=z.dtype, device=dev) if last else None
-        ws = _workspace(dev, "gcn_bwd_sync", _lib.load().sgf_gcn_bn_bwd_dx_workspace_bytes(n, d))
-        with torch.cuda.device(dev):
-            _lib.call("sgf_gcn_bn_bwd_dx", _ptr(gy), _ld(gy), _ptr(z), _ld(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta),
-                      int(relu), _ptr(stats), float(inv_n), int(training), _ptr(w), w.stride(0), n, d, _code(z), _ptr(dz),
-                      _ld(dz), _ptr(dy), _ld(dy), _ptr(acc_in), _ptr(acc_out), nbytes, _ptr(dx0), _ld(dx0), int(add_gy),
-                      _ptr(ws), ws.numel(), _stream(dev))
+        _launch(dev, "sgf_gcn_bn_bwd_dx", gy, _ld(gy), z, _ld(z), mean, rstd, gamma, beta, int(relu), stats, float(inv_n),
+                int(training), w, w.stride(0), n, d, _code(z), dz, _ld(dz), dy, _ld(dy), acc_in, acc_out, nbytes, dx0, _ld(dx0),
+                int(add_gy), *_scratch(dev, "gcn_bwd_sync", _lib.load().sgf_gcn_bn_bwd_dx_workspace_bytes(n, d)))
         return dz, dy, (dx0 if last else acc_out)
 
     @staticmethod
@@ -1406,10 +1295,8 @@ class HipKernels:
         dx1 = torch.empty((n, d), dtype=dy.dtype, device=dy.device)
         dx2 = torch.empty((n, d), dtype=dy.dtype, device=dy.device)
         assert w1.stride(0) == w2.stride(0)
-        with torch.cuda.device(dy.device):
-            _lib.call("sgf_gcn_epilogue_dx2", _ptr(dy), _ld(dy), _ptr(w1), _ptr(w2), w1.stride(0), n, d,
-                      _mm_code(dy, "sgf_gcn_epilogue_supported", d, d),
-                      _ptr(dx1), _ld(dx1), _ptr(dx2), _ld(dx2), int(pair), _stream(dy.device))
+        _launch(dy.device, "sgf_gcn_epilogue_dx2", dy, _ld(dy), w1, w2, w1.stride(0), n, d,
+                _mm_code(dy, "sgf_gcn_epilogue_supported", d, d), dx1, _ld(dx1), dx2, _ld(dx2), int(pair))
         return dx1, dx2
 
     # ---- T7 ----
@@ -1417,7 +1304,5 @@ class HipKernels:
     def axpby(x1, a: float, x2, b: float) -> torch.Tensor:
         n, d = x1.shape
         y = torch.empty((n, d), dtype=x1.dtype, device=x1.device)
-        with torch.cuda.device(x1.device):
-            _lib.call("sgf_axpby", _ptr(x1), _ld(x1), float(a), _ptr(x2), _ld(x2), float(b), n, d,
-                      _code(x1), _ptr(y), y.stride(0), _stream(x1.device))
+        _launch(x1.device, "sgf_axpby", x1, _ld(x1), float(a), x2, _ld(x2), float(b), n, d, _code(x1), y, y.stride(0))
         return y

@@ -25,8 +25,8 @@ import torch
 
 from . import _lib
 from . import kernels as _kernels
-from .kernels import (HipKernels, LONG_ROW, _SEGMENT, _code, _ld, _one_pass_cat, _pair_gram, _ptr, _rows,  # noqa: F401
-                      _rows16, _stream, _workspace, _workspaces)
+from .kernels import HipKernels, LONG_ROW, _SEGMENT, _workspace  # noqa: F401  (re-exported: tests, graphed.py)
+from .kernels import _rows, _rows16
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16

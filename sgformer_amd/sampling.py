@@ -16,15 +16,13 @@ std::mt19937's: parity is structural (tests/test_gpu_sampler.py, oracle/graph_or
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional, Sequence
 
 import torch
 
 from . import _lib, ops
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .kernels import _launch, _scratch
 
 
 class SampledBatch:
@@ -88,7 +86,6 @@ def _sampled_csr() -> bool:
     """SGF_SAMPLED_CSR=0: a sampled batch carries its edge list only and ops.CSRGraph sorts it (sgf_csr_build, and
     sgf_csr_transpose with its host read in the first backward), as before sgf_sampled_csr_*; any other value: the batch
     comes with the CSR sgf_sampled_csr_build made."""
-    import os
     return os.environ.get("SGF_SAMPLED_CSR", SAMPLED_CSR_DEFAULT) != "0"
 
 
@@ -126,27 +123,25 @@ class NeighborSampler:
         bs = int(seeds32.numel())
         batch_id = self.batches if batch_id is None else int(batch_id)
         self.batches += 1
-        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if self._fan_dev is not None and self._batch_capacity(bs) <= _ONE_CALL_MAX_ENTRIES:
-            return self._sample_batch(seeds32, bs, batch_id, st)
+            return self._sample_batch(seeds32, bs, batch_id)
         # deep / wide fan-outs: the one-call form sizes every buffer to the worst case bs * (k1 + k1 k2 + ...) BEFORE any
         # de-duplication (GBs per batch for e.g. [25, 20, 15, 10] at 1024 seeds); hop by hop the buffers follow the
         # actual frontier
         nodes = [seeds32]
         srcs, dsts = [], []
-        with torch.cuda.device(dev):
-            _lib.call("sgf_neighbor_sample_mark", _ptr(self.local_of), _ptr(seeds32), bs, 0, st)
-            frontier, local0, n_known = seeds32, 0, bs
-            try:
-                self._hops(st, nodes, srcs, dsts, frontier, local0, n_known, batch_id)
-            except BaseException:
-                # a hop failed (workspace, allocation, fan-out overflow): its kernel may have marked nodes that never made
-                # it into `nodes` — stale marks would hand out-of-range local ids to the next batch.  Reset the whole table.
-                self.local_of.fill_(torch.iinfo(torch.int32).min)
-                raise
-            # back to "not in a batch" for every id of this batch
-            n_id32 = torch.cat(nodes)
-            _lib.call("sgf_neighbor_sample_mark", _ptr(self.local_of), _ptr(n_id32), int(n_id32.numel()), -1, st)
+        _launch(dev, "sgf_neighbor_sample_mark", self.local_of, seeds32, bs, 0)
+        frontier, local0, n_known = seeds32, 0, bs
+        try:
+            self._hops(nodes, srcs, dsts, frontier, local0, n_known, batch_id)
+        except BaseException:
+            # a hop failed (workspace, allocation, fan-out overflow): its kernel may have marked nodes that never made
+            # it into `nodes` — stale marks would hand out-of-range local ids to the next batch.  Reset the whole table.
+            self.local_of.fill_(torch.iinfo(torch.int32).min)
+            raise
+        # back to "not in a batch" for every id of this batch
+        n_id32 = torch.cat(nodes)
+        _launch(dev, "sgf_neighbor_sample_mark", self.local_of, n_id32, int(n_id32.numel()), -1)
         ei = torch.stack([torch.cat(srcs), torch.cat(dsts)]).long() if srcs else torch.zeros(2, 0, dtype=torch.int64, device=dev)
         ei._sgf_trusted = True          # local ids are in range by construction: ops.CSRGraph skips its host check
         return n_id32.long(), ei, bs
@@ -159,7 +154,7 @@ class NeighborSampler:
             total += width
         return total
 
-    def _sample_batch(self, seeds32, bs, batch_id, st):
+    def _sample_batch(self, seeds32, bs, batch_id):
         dev = self.device
         lib = _lib.load()
         ncap, ecap = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -171,15 +166,13 @@ class NeighborSampler:
         e_src = torch.empty(max(ecap, 1), dtype=torch.int32, device=dev)
         e_dst = torch.empty(max(ecap, 1), dtype=torch.int32, device=dev)
         counts = torch.empty(2 + 2 * len(self.fanouts), dtype=torch.int64, device=dev)
-        ws = ops._workspace(dev, "nbr_sample", nbytes)
-        with torch.cuda.device(dev):
-            try:
-                _lib.call("sgf_neighbor_sample_batch", _ptr(self.rowptr), _ptr(self.colind), _ptr(seeds32), bs, self._fan_host,
-                          len(self.fanouts), ctypes.c_uint64(self.seed), ctypes.c_uint64(batch_id), _ptr(self.local_of),
-                          _ptr(nodes), ncap, _ptr(e_src), _ptr(e_dst), ecap, _ptr(counts), _ptr(ws), ws.numel(), st)
-            except BaseException:
-                self.local_of.fill_(torch.iinfo(torch.int32).min)
-                raise
+        try:
+            _launch(dev, "sgf_neighbor_sample_batch", self.rowptr, self.colind, seeds32, bs, self._fan_host, len(self.fanouts),
+                    ctypes.c_uint64(self.seed), ctypes.c_uint64(batch_id), self.local_of, nodes, ncap, e_src, e_dst, ecap,
+                    counts, *_scratch(dev, "nbr_sample", nbytes))
+        except BaseException:
+            self.local_of.fill_(torch.iinfo(torch.int32).min)
+            raise
         # the batch's normalised CSR from the edges as they were emitted (targets already in order, rows of at most
         # max(fanouts) entries: sgf_sampled_csr_build) — queued BEFORE the host read, sized by the capacities
         csr = None
@@ -196,7 +189,7 @@ class NeighborSampler:
             ei._sgf_csr_t_lazy = True       # ... and transposes them with sgf_sampled_csr_transpose (no symmetry test, no host read)
         return nodes[:nn].long(), ei, bs
 
-    def _hops(self, st, nodes, srcs, dsts, frontier, local0, n_known, batch_id):
+    def _hops(self, nodes, srcs, dsts, frontier, local0, n_known, batch_id):
         """The hop-by-hop path (a fan-out of -1 has no a-priori capacity): one sgf_neighbor_sample_hop per hop, its edge and
         node counts read back to size the next hop's buffers."""
         dev = self.device
@@ -210,11 +203,9 @@ class NeighborSampler:
             s_glob = torch.empty(cap, dtype=torch.int32, device=dev)
             new = torch.empty(cap, dtype=torch.int32, device=dev)
             counts = torch.zeros(2, dtype=torch.int64, device=dev)
-            nbytes = _lib.load().sgf_neighbor_sample_workspace_bytes(m, cap)
-            ws = ops._workspace(dev, "nbr_sample", nbytes)
-            _lib.call("sgf_neighbor_sample_hop", _ptr(self.rowptr), _ptr(self.colind), _ptr(frontier), m, local0, k,
-                      ctypes.c_uint64(self.seed), ctypes.c_uint64(batch_id), hop, _ptr(self.local_of), n_known, cap,
-                      _ptr(e_src), _ptr(e_dst), _ptr(s_glob), _ptr(new), _ptr(counts), _ptr(ws), ws.numel(), st)
+            _launch(dev, "sgf_neighbor_sample_hop", self.rowptr, self.colind, frontier, m, local0, k, ctypes.c_uint64(self.seed),
+                    ctypes.c_uint64(batch_id), hop, self.local_of, n_known, cap, e_src, e_dst, s_glob, new, counts,
+                    *_scratch(dev, "nbr_sample", _lib.load().sgf_neighbor_sample_workspace_bytes(m, cap)))
             ne, nn = (int(v) for v in counts.tolist())
             self.host_reads += 2        # this one and the edge count inside sgf_neighbor_sample_hop
             srcs.append(e_src[:ne])

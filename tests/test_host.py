@@ -54,6 +54,32 @@ def test_header_binding_and_library_agree():
     assert lib.sgf_attn_bstats_len(1, 256) == 256 * 256 + 256 + 1
 
 
+def test_header_constants_are_mirrored_by_the_binding():
+    """Every `#define SGF_<NAME> <integer>` of include/sgf.h except SGF_VERSION (dtype codes, status codes, target kinds)
+    has the same value in sgformer_amd/_lib.py."""
+    from sgformer_amd import _lib
+    src = open(os.path.join(ROOT, "include", "sgf.h")).read()
+    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SGF_\w+)\s+\(?(-?\d+)\)?", src, flags=re.M)}
+    defs.pop("SGF_VERSION")
+    assert {"SGF_F32", "SGF_BF16", "SGF_OK", "SGF_E_HIP", "SGF_BCE_TARGET_CLASS", "SGF_METRIC_TARGET_I64"} <= set(defs)
+    assert len(defs) >= 13
+    for name, value in defs.items():
+        assert getattr(_lib, name, None) == value, name
+
+
+def test_dtype_without_a_code_never_reaches_the_library(monkeypatch):
+    """float16 / float64 have no dtype code: tile_supported answers False and lds_rows_max raises the TypeError of _code,
+    neither asks the library about float32 on the caller's behalf (the stand-in has no entry to call)."""
+    from sgformer_amd import _lib, kernels
+    monkeypatch.setattr(_lib, "_lib", object())
+    for dtype in (torch.float16, torch.float64):
+        assert kernels.HipKernels.tile_supported(64, dtype) is False
+        with pytest.raises(TypeError, match="float32 or bfloat16"):
+            kernels.HipKernels.lds_rows_max(dtype)
+        with pytest.raises(TypeError, match="float32 or bfloat16"):
+            kernels._code(torch.zeros(1, dtype=dtype))
+
+
 def test_argument_errors_are_reported_per_thread():
     """Bad arguments are rejected on the host BEFORE any HIP call (safe without a GPU) with
     SGF_E_INVALID and an errno-style, per-thread message."""
