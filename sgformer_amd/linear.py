@@ -3,13 +3,13 @@ large/ours.py (:123-126, :36-40, :77, :198, :275), the two input stems with thei
 layer's Linear + BatchNorm + relu + residual with its chained input gradients.  `ops` re-exports every name."""
 from __future__ import annotations
 
-import ctypes
-from collections import OrderedDict
-from typing import Optional
+import os
+from functools import partial
+from typing import NamedTuple, Optional
 
 import torch
+import torch.nn.functional as F
 
-from . import _lib
 from .kernels import _pair_gram, _rows, _rows16
 
 _F32 = torch.float32
@@ -18,35 +18,88 @@ _BF16 = torch.bfloat16
 from .graph import K  # noqa: E402,F401  (ONE kernel table, rebound in every module by ops.set_kernels)
 
 
+def _f32c(t):
+    """A parameter (or None) as the kernels read it: fp32, contiguous, outside autograd."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _has(table, name: str, *args) -> bool:
+    """The kernel table has the method `name` — and, given arguments, answers them with yes (the *_supported queries).
+    hasattr is the rule on purpose: the CPU table of the tests lacks methods."""
+    fn = getattr(table, name, None)
+    return fn is not None and (not args or bool(fn(*args)))
+
+
+def _switch(name: str, default: bool) -> bool:
+    """The environment switch `name`: on by default and turned off with 0, or off by default and turned on with 1.  Read on
+    every call — the tests flip switches at run time."""
+    v = os.environ.get(name)
+    return default if v is None else (v != "0" if default else v == "1")
+
+
 # BatchNorm's batch statistics of a tensor (large/ours.py:77-81, :87-88): shifted one-pass column sums
 _BN_SAMPLE_ROWS = 1024
 
 
-def batch_stats(x: torch.Tensor, shard=None):
-    """Column mean / biased variance over all rows (all ranks when sharded) in ONE pass over x.
+class BNSums(NamedTuple):
+    """What the statistics pass leaves of a [n, d] tensor: sums = [sum (x - shift) | sum (x - shift)^2] over all rows (all
+    ranks when sharded) in fp32, the shift they were taken about, and the row count."""
+    sums: torch.Tensor
+    shift: Optional[torch.Tensor]
+    count: float
 
-    Shifted single pass: the shift is the column mean of a small leading sample of rows (a ~10 us
-    kernel), then one streaming pass accumulates [sum (x - s) | sum (x - s)^2] in fp32;
-    mean = s + m1, var = m2 - m1^2 with m1 ~ sigma / sqrt(sample) — no cancellation, unlike the
-    unshifted E[x^2] - E[x]^2, and half the HBM traffic of the two-pass form.  Node-sharded runs
-    all-reduce the sample sums (so that every rank uses the same shift) and then the two sums."""
-    K.check(x)
-    x = _rows(x.detach())
-    n, d = x.shape
+    def moments(self):
+        """(mean, biased variance, count): mean = shift + m1, var = m2 - m1^2 with m1 ~ sigma / sqrt(sample) — no
+        cancellation, unlike the unshifted E[x^2] - E[x]^2."""
+        d = self.sums.numel() // 2
+        m1 = self.sums[:d] / max(self.count, 1.0)
+        mean = m1 if self.shift is None else self.shift + m1
+        return mean, (self.sums[d:] / max(self.count, 1.0) - m1 * m1).clamp_min_(0.0), self.count
+
+
+def _shifted_sums(launch, d: int, n: int, device, shard):
+    """(out, BNSums) of a producer of n rows of width d in ONE pass over its operand.  `launch(rows, shift, want_stats)` runs
+    the producer on the first `rows` rows (None: all) and returns (its output, the sums about `shift`).
+
+    The shift is the column mean of a small leading sample of rows (a ~10 us launch), then the full launch accumulates the
+    shifted sums — half the HBM traffic of the two-pass form.  Node-sharded runs all-reduce the sample sums with their count
+    (so that every rank uses the same shift) and then the two sums."""
     ns = min(n, _BN_SAMPLE_ROWS)
-    samp = torch.cat([K.colstats(x[:ns], None)[:d], torch.full((1,), float(ns), dtype=_F32, device=x.device)])
-    n_tot = float(n)
-    if shard is not None:
+    _, st_s = launch(ns, None, True)
+    count = float(n)
+    if shard is None:
+        shift = st_s[:d] * (1.0 / float(max(ns, 1)))          # one launch; the sharded form needs the global sample count
+    else:
+        samp = torch.cat([st_s[:d], torch.full((1,), float(ns), dtype=_F32, device=device)])
         shard.all_reduce(samp)
-        n_tot = float(shard.n_global)
-    shift = (samp[:d] / samp[d].clamp_min(1.0)).contiguous()
-    st = K.colstats(x, shift)
+        count = float(shard.n_global)
+        shift = (samp[:d] / samp[d].clamp_min(1.0)).contiguous()
+    out, st = launch(None, shift, True)
     if shard is not None:
         shard.all_reduce(st)
-    m1 = st[:d] / max(n_tot, 1.0)
-    mean = shift + m1
-    var = (st[d:] / max(n_tot, 1.0) - m1 * m1).clamp_min_(0.0)
-    return mean, var, n_tot
+    return out, BNSums(st, shift, count)
+
+
+def _column_sums(x: torch.Tensor, shard=None) -> BNSums:
+    x = _rows(x.detach())
+    return _shifted_sums(lambda rows, shift, _: (None, K.colstats(x if rows is None else x[:rows], shift)),
+                         x.shape[1], x.shape[0], x.device, shard)[1]
+
+
+def batch_stats(x: torch.Tensor, shard=None):
+    """Column mean / biased variance over all rows (all ranks when sharded) in ONE pass over x (sgf_colstats)."""
+    K.check(x)
+    return _column_sums(x, shard).moments()
+
+
+def _bn_param_grads(stats, d: int, g32, be32, dtype, shard):
+    """(d gamma, d beta) out of BatchNorm backward's sums [sum dz | sum dz xhat].  Node-sharded: the sums are global already
+    and ShardContext.sync_grads sums parameter gradients over the ranks again — pre-divide."""
+    dgamma = stats[d:].to(dtype) if g32 is not None else None
+    dbeta = stats[:d].to(dtype) if be32 is not None else None
+    if shard is not None and g32 is not None:
+        dgamma, dbeta = shard.unsum(dgamma), shard.unsum(dbeta)
+    return dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------------
@@ -66,7 +119,8 @@ class _Linear(torch.autograd.Function):
     without materialising the concatenation)."""
 
     @staticmethod
-    def forward(ctx, w, b, stats_req, *xs):
+    def forward(ctx, w, b, want_stats: bool, shard, *xs):
+        """(y, BNSums of y for the BatchNorm that follows — None unless asked for)."""
         K.check(*xs)
         dt = xs[0].dtype
         wc = w if w.dtype == dt else w.to(dt)
@@ -79,36 +133,30 @@ class _Linear(torch.autograd.Function):
             # streaming passes with W resident in LDS (sgf_gcn_epilogue_*); the BatchNorm that follows gets its
             # column sums from the same pass
             xr = [_rows16(x) for x in xs]
-            b32 = None if b is None else b.detach().float().contiguous()
-            if stats_req is not None:
-                y = _linear_with_stats(xr, wc, b32, stats_req)
-            else:
-                y, _ = _streaming_linear(xr, wc, b32)
+            y, stats = _linear_with_stats(xr, wc, _f32c(b), shard) if want_stats else _streaming_linear(xr, wc, _f32c(b))
         else:
             # any other shape (input widths beyond 256 or not multiples of 4, odd hidden widths, multi-head projections):
             # the general matrix-core kernel (sgf_gemm, csrc/gemm.hip) — first operand with the bias, the rest accumulated
             # IN PLACE; W's column blocks are passed as strided views (no copy, no transposition)
-            b32 = None if b is None else b.detach().float().contiguous()
-            y = K.gemm(xs[0], wc[:, :widths[0]].t(), bias=b32)
+            y = K.gemm(xs[0], wc[:, :widths[0]].t(), bias=_f32c(b))
             off = widths[0]
             for x, k in zip(xs[1:], widths[1:]):
                 K.gemm(x, wc[:, off:off + k].t(), out=y, beta=1.0, addend=y)
                 off += k
-        if stats_req is not None and not fused:
-            stats_req["out"] = batch_stats(y, stats_req.get("shard"))
+            stats = _column_sums(y, shard) if want_stats else None
         ctx.save_for_backward(wc, *xs)
         ctx.meta = (w.dtype, None if b is None else b.dtype, widths)
-        return y
+        return y, stats
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, _):
         wc, *xs = ctx.saved_tensors
         wdtype, bdtype, widths = ctx.meta
         g = g.contiguous()
         need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and bdtype is not None
         dxs, off = [], 0
         for i, k in enumerate(widths):
-            if not ctx.needs_input_grad[3 + i]:
+            if not ctx.needs_input_grad[4 + i]:
                 dxs.append(None)
             elif _streaming_linear_ok(g, wc[:, off:off + k], dx=True):
                 dxs.append(K.gcn_epilogue_dx(_rows16(g), wc[:, off:off + k]))
@@ -116,7 +164,7 @@ class _Linear(torch.autograd.Function):
                 dxs.append(K.gemm(g, wc[:, off:off + k]))
             off += k
         dw, db = _linear_param_grads(g, xs, widths, need_w, need_b, wdtype, bdtype)
-        return (dw, db, None, *dxs)
+        return (dw, db, None, None, *dxs)
 
 
 def _linear_param_grads(g, xs, widths, need_w, need_b, wdtype, bdtype):
@@ -126,10 +174,10 @@ def _linear_param_grads(g, xs, widths, need_w, need_b, wdtype, bdtype):
         # sgf_gram wants widths that are multiples of 4 elements: zero-pad the odd ones (e.g. the
         # C = 47 logits gradient: one extra [N, 48] pass) and slice the result
         m = g.shape[1]
-        gp = _rows(g if m % 4 == 0 else torch.nn.functional.pad(g, (0, 4 - m % 4)))
+        gp = _rows(g if m % 4 == 0 else F.pad(g, (0, 4 - m % 4)))
         dw = torch.empty((gp.shape[1], sum(widths)), dtype=_F32, device=g.device)
         off = 0
-        if (len(xs) == 2 and widths[0] == widths[1] and widths[0] % 4 == 0 and hasattr(K, "gram2") and gp.dtype == _BF16
+        if (len(xs) == 2 and widths[0] == widths[1] and widths[0] % 4 == 0 and _has(K, "gram2") and gp.dtype == _BF16
                 and xs[0].dtype == _BF16 and xs[1].dtype == _BF16 and _pair_gram()):
             # both blocks of dW = g^T [x_1 | x_2] from ONE read of g out of HBM (paired launch, sgf_gram2)
             k = widths[0]
@@ -142,7 +190,7 @@ def _linear_param_grads(g, xs, widths, need_w, need_b, wdtype, bdtype):
                 blk, cs = K.gram(gp, _rows(x), want_colsum=(i == 0 and need_b))
                 dw[:, off:off + k] = blk
             else:
-                xp = _rows(torch.nn.functional.pad(x, (0, 4 - k % 4)))
+                xp = _rows(F.pad(x, (0, 4 - k % 4)))
                 blk, cs = K.gram(gp, xp, want_colsum=(i == 0 and need_b))
                 dw[:, off:off + k] = blk[:, :k]
             if i == 0:
@@ -153,41 +201,50 @@ def _linear_param_grads(g, xs, widths, need_w, need_b, wdtype, bdtype):
     return dw, db
 
 
+def _batchnorm_of(book, launch, d: int, n: int, device, shard):
+    """(the output of `launch`, mean, rstd, count, used batch statistics): a producer's output and the BatchNorm that `book`
+    — the module's bookkeeping, ours._BNBook — decides for it: batch statistics out of the producer's own pass (the running
+    ones updated on the way), or the running statistics."""
+    if book.use_batch():
+        out, stats = _shifted_sums(launch, d, n, device, shard)
+        mean, rstd, count, used = book.from_sums(stats)
+    else:
+        out = launch(None, None, False)[0]
+        mean, rstd, count, used = book.running()
+    return out, _f32c(mean), _f32c(rstd), count, used
+
+
+def _stem_launch(x, w0c, w1c, b32):
+    """Both stems as a `launch` of _shifted_sums: ((y0, y1), sums of y0); the statistics sample computes y0 alone."""
+    def launch(rows, shift, want_stats):
+        if rows is not None:
+            return None, K.stem_pair(x[:rows], w0c, b32[0], None, None, None, want_stats0=True)[2]
+        y0, y1, st = K.stem_pair(x, w0c, b32[0], w1c, b32[1], shift, want_stats0=want_stats)
+        return (y0, y1), st
+    return launch
+
+
 class _StemPair(torch.autograd.Function):
-    """(y0, y1) = (x W0^T + b0, x W1^T + b1) from ONE pass over x — the first Linear of GraphConv and of TransConv
-    (large/ours.py:77, :198) read the same node features; y0's BatchNorm column sums ride along (stats_req)."""
+    """(y0, y1, BNSums of y0 or None) with (y0, y1) = (x W0^T + b0, x W1^T + b1) from ONE pass over x — the first Linear of
+    GraphConv and of TransConv (large/ours.py:77, :198) read the same node features; the column sums y0's BatchNorm needs
+    ride along when asked for."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1, stats_req):
+    def forward(ctx, x, w0, b0, w1, b1, want_stats: bool, shard):
         K.check(x)
         dt = x.dtype
         w0c, w1c = w0.to(dt), w1.to(dt)
-        f32 = [None if b is None else b.detach().float().contiguous() for b in (b0, b1)]
-        d = w0.shape[0]
-        shift = None
-        if stats_req is not None:
-            shard = stats_req.get("shard")
-            n = x.shape[0]
-            ns = min(n, _BN_SAMPLE_ROWS)
-            _, _, st_s = K.stem_pair(x[:ns], w0c, f32[0], None, None, None, want_stats0=True)
-            samp = torch.cat([st_s[:d], torch.full((1,), float(ns), dtype=_F32, device=x.device)])
-            n_tot = float(n)
-            if shard is not None:
-                shard.all_reduce(samp)
-                n_tot = float(shard.n_global)
-            shift = (samp[:d] / samp[d].clamp_min(1.0)).contiguous()
-        y0, y1, st = K.stem_pair(x, w0c, f32[0], w1c, f32[1], shift, want_stats0=stats_req is not None)
-        if stats_req is not None:
-            if shard is not None:
-                shard.all_reduce(st)
-            m1 = st[:d] / max(n_tot, 1.0)
-            stats_req["out"] = (shift + m1, (st[d:] / max(n_tot, 1.0) - m1 * m1).clamp_min_(0.0), n_tot)
+        launch = _stem_launch(x, w0c, w1c, [_f32c(b0), _f32c(b1)])
+        if want_stats:
+            (y0, y1), stats = _shifted_sums(launch, w0.shape[0], x.shape[0], x.device, shard)
+        else:
+            (y0, y1), stats = launch(None, None, False)[0], None
         ctx.save_for_backward(x, w0c, w1c)
         ctx.meta = (w0.dtype, None if b0 is None else b0.dtype, w1.dtype, None if b1 is None else b1.dtype)
-        return y0, y1
+        return y0, y1, stats
 
     @staticmethod
-    def backward(ctx, g0, g1):
+    def backward(ctx, g0, g1, _):
         x, w0c, w1c = ctx.saved_tensors
         wd0, bd0, wd1, bd1 = ctx.meta
         k = [x.shape[1]]
@@ -199,7 +256,7 @@ class _StemPair(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = K.gemm(g0.contiguous(), w0c)
             K.gemm(g1.contiguous(), w1c, out=dx, beta=1.0, addend=dx)
-        return dx, dw0, db0, dw1, db1, None
+        return dx, dw0, db0, dw1, db1, None, None
 
 
 class _StemPairBN(torch.autograd.Function):
@@ -210,7 +267,7 @@ class _StemPairBN(torch.autograd.Function):
     (sgf_gram_bn_bwd): x is data, nobody else needs dz."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, ln_gamma=None, ln_beta=None, ln_cfg=None, pack=None):
+    def forward(ctx, x, w0, b0, w1, b1, gamma, beta, book, shard, ln_gamma=None, ln_beta=None, ln_cfg=None, pack=None):
         """ln_cfg = (eps, relu, affine) — not None: the third output is [relu](LayerNorm(y1)) (TransConv's stem, large/ours.py:
         198-201) instead of y1, and its backward takes dW1 / db1 / d ln_gamma / d ln_beta from sgf_gram_ln_bwd.
         pack = {"slot_bytes": S} — not None: the BatchNorm pass also writes x0 in packed form for the SpMM that gathers it
@@ -218,37 +275,9 @@ class _StemPairBN(torch.autograd.Function):
         K.check(x)
         dt = x.dtype
         w0c, w1c = w0.to(dt), w1.to(dt)
-        f32 = [None if b is None else b.detach().float().contiguous() for b in (b0, b1)]
-        d = w0.shape[0]
-        n = x.shape[0]
-        want = bn_hook(None)
-        shift = None
-        if want:
-            ns = min(n, _BN_SAMPLE_ROWS)
-            _, _, st_s = K.stem_pair(x[:ns], w0c, f32[0], None, None, None, want_stats0=True)
-            n_tot = float(n)
-            if shard is None:
-                shift = st_s[:d] * (1.0 / float(max(ns, 1)))
-            else:
-                samp = torch.cat([st_s[:d], torch.full((1,), float(ns), dtype=_F32, device=x.device)])
-                shard.all_reduce(samp)
-                n_tot = float(shard.n_global)
-                shift = (samp[:d] / samp[d].clamp_min(1.0)).contiguous()
-        y0, y1, st = K.stem_pair(x, w0c, f32[0], w1c, f32[1], shift, want_stats0=want)
-        if want:
-            if shard is not None:
-                shard.all_reduce(st)
-            if hasattr(K, "bn_finalize"):
-                mean, rstd, n_tot, training = bn_hook(("raw", st, shift, n_tot))
-            else:
-                m1 = st[:d] / max(n_tot, 1.0)
-                mean, rstd, n_tot, training = bn_hook((shift + m1, (st[d:] / max(n_tot, 1.0) - m1 * m1).clamp_min_(0.0), n_tot))
-        else:
-            mean, rstd, n_tot, training = bn_hook(False)
-        g32 = gamma.detach().float().contiguous() if gamma is not None else None
-        be32 = beta.detach().float().contiguous() if beta is not None else None
-        mean = mean.detach().float().contiguous()
-        rstd = rstd.detach().float().contiguous()
+        (y0, y1), mean, rstd, n_tot, training = _batchnorm_of(book, _stem_launch(x, w0c, w1c, [_f32c(b0), _f32c(b1)]),
+                                                              w0.shape[0], x.shape[0], x.device, shard)
+        g32, be32 = _f32c(gamma), _f32c(beta)
         if pack is not None:
             x0, pack["out"] = K.bn_apply_packed(y0, mean, rstd, g32, be32, None, True, pack["slot_bytes"])
         else:
@@ -256,8 +285,7 @@ class _StemPairBN(torch.autograd.Function):
         out1, ln_saved = y1, (None, None, None, None, None)
         if ln_cfg is not None:
             eps, ln_relu, affine = ln_cfg
-            lg32 = ln_gamma.detach().float().contiguous() if affine else None
-            lb32 = ln_beta.detach().float().contiguous() if affine else None
+            lg32, lb32 = (_f32c(ln_gamma), _f32c(ln_beta)) if affine else (None, None)
             out1, lmean, lrstd = K.ln_fwd(_rows(y1), None, 1.0, 0.0, lg32, lb32, bool(ln_relu), float(eps))
             ln_saved = (y1, lmean, lrstd, lg32, lb32)
         ctx.save_for_backward(x, w0c, w1c, y0, g32, be32, mean, rstd, *ln_saved)
@@ -295,10 +323,7 @@ class _StemPairBN(torch.autograd.Function):
         else:
             dw1, db1 = _linear_param_grads(g1.contiguous(), [x], [x.shape[1]], ctx.needs_input_grad[3],
                                            ctx.needs_input_grad[4] and bd1 is not None, wd1, bd1)
-        dgamma = stats[d:].to(gdt) if g32 is not None else None
-        dbeta = stats[:d].to(gdt) if be32 is not None else None
-        if shard is not None and g32 is not None:
-            dgamma, dbeta = shard.unsum(dgamma), shard.unsum(dbeta)
+        dgamma, dbeta = _bn_param_grads(stats, d, g32, be32, gdt, shard)
         dx = None
         if ctx.needs_input_grad[0]:                      # features that require a gradient (not in any recipe): explicit dz
             g = ga if gb is None else ga + gb
@@ -316,23 +341,22 @@ class _StemPairBN(torch.autograd.Function):
 
 
 def stem_pair_bn_supported(x, w0, w1) -> bool:
-    return (stem_pair_supported(x, w0, w1) and hasattr(K, "gram_bn_bwd_supported")
-            and K.gram_bn_bwd_supported(w0.shape[0], x.shape[1], x.dtype))
+    return stem_pair_supported(x, w0, w1) and _has(K, "gram_bn_bwd_supported", w0.shape[0], x.shape[1], x.dtype)
 
 
-def stem_pair_bn(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard=None, ln=None, pack=None):
-    """(x0 for the layers, x0 for the first SpMM, y1): see _StemPairBN.  ln = (LayerNorm weight, bias, eps, relu): the third
-    output is [relu](LayerNorm(y1)) — TransConv's stem — when the shapes allow (stem_ln_supported).  pack: see _StemPairBN."""
+def stem_pair_bn(x, w0, b0, w1, b1, gamma, beta, book, shard=None, ln=None, pack=None):
+    """(x0 for the layers, x0 for the first SpMM, y1): see _StemPairBN.  book: the BatchNorm's bookkeeping (ours._BNBook).
+    ln = (LayerNorm weight, bias, eps, relu): the third output is [relu](LayerNorm(y1)) — TransConv's stem — when the shapes
+    allow (stem_ln_supported).  pack: see _StemPairBN."""
     if ln is None:
-        return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, None, None, None, pack)
+        return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, book, shard, None, None, None, pack)
     lg, lb, eps, relu = ln
-    return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, bn_hook, shard, lg, lb, (eps, relu, lg is not None), pack)
+    return _StemPairBN.apply(x, w0, b0, w1, b1, gamma, beta, book, shard, lg, lb, (eps, relu, lg is not None), pack)
 
 
 def stem_ln_supported(x, w1) -> bool:
-    import os
-    return (hasattr(K, "gram_ln_bwd_supported") and K.gram_ln_bwd_supported(w1.shape[0], x.shape[1], x.dtype)
-            and not x.requires_grad and os.environ.get("SGF_STEM_LN_FUSED", "1") != "0")
+    return (_has(K, "gram_ln_bwd_supported", w1.shape[0], x.shape[1], x.dtype) and not x.requires_grad
+            and _switch("SGF_STEM_LN_FUSED", True))
 
 
 def stem_pair_supported(x, w0, w1) -> bool:
@@ -344,9 +368,8 @@ def stem_pair_supported(x, w0, w1) -> bool:
 def stem_pair(x, w0, b0, w1, b1, want_stats0=False, shard=None):
     """((y0, y1), stats0): both input stems from one read of x; stats0 = (mean, var, count) of y0 for its BatchNorm
     when asked for, else None."""
-    req = {"shard": shard, "out": None} if want_stats0 else None
-    y0, y1 = _StemPair.apply(x, w0, b0, w1, b1, req)
-    return (y0, y1), (req["out"] if req is not None else None)
+    y0, y1, stats = _StemPair.apply(x, w0, b0, w1, b1, bool(want_stats0), shard)
+    return (y0, y1), (None if stats is None else stats.moments())
 
 
 def _streaming_linear_ok(x: torch.Tensor, wc: torch.Tensor, dx: bool = False) -> bool:
@@ -356,38 +379,18 @@ def _streaming_linear_ok(x: torch.Tensor, wc: torch.Tensor, dx: bool = False) ->
             and K.gcn_epilogue_supported(wc.shape[1], wc.shape[0], x.dtype))
 
 
-def _streaming_linear(xr, wc, b32, shift=None, want_stats=False, rows=None):
-    """[x_1 | x_2] wc^T + b32 on the first `rows` rows (all by default): one or two streaming passes."""
+def _streaming_linear(xr, wc, b32, rows=None, shift=None, want_stats=False):
+    """([x_1 | x_2] wc^T + b32 on the first `rows` rows (all by default), its sums about `shift` if wanted): one or two
+    streaming passes — a `launch` of _shifted_sums once the operands are bound."""
     xs = xr if rows is None else [x[:rows] for x in xr]
     if len(xs) == 1:
         return K.gcn_epilogue_stats(xs[0], wc, b32, shift, want_stats=want_stats)
     return K.gcn_epilogue_cat(xs[0], xs[1], wc, b32, shift, want_stats=want_stats)
 
 
-def _linear_with_stats(xr, wc, b32, stats_req):
-    """y = [x_1 | x_2] wc^T + b32 AND BatchNorm's batch statistics of y, from the same pass.  Same shifted sums as
-    batch_stats: the shift is the column mean of the first rows of y, which a small launch over those rows provides."""
-    shard = stats_req.get("shard")
-    n, d = xr[0].shape[0], wc.shape[0]
-    ns = min(n, _BN_SAMPLE_ROWS)
-    _, st_s = _streaming_linear(xr, wc, b32, None, want_stats=True, rows=ns)
-    n_tot = float(n)
-    if shard is None:
-        shift = st_s[:d] * (1.0 / float(max(ns, 1)))          # one launch; the sharded form needs the global sample count
-    else:
-        samp = torch.cat([st_s[:d], torch.full((1,), float(ns), dtype=_F32, device=xr[0].device)])
-        shard.all_reduce(samp)
-        n_tot = float(shard.n_global)
-        shift = (samp[:d] / samp[d].clamp_min(1.0)).contiguous()
-    y, st = _streaming_linear(xr, wc, b32, shift, want_stats=True)
-    if shard is not None:
-        shard.all_reduce(st)
-    if stats_req.get("raw"):
-        stats_req["out"] = ("raw", st, shift, n_tot)              # the caller finalises (K.bn_finalize: one launch)
-        return y
-    m1 = st[:d] / max(n_tot, 1.0)
-    stats_req["out"] = (shift + m1, (st[d:] / max(n_tot, 1.0) - m1 * m1).clamp_min_(0.0), n_tot)
-    return y
+def _linear_with_stats(xr, wc, b32, shard):
+    """(y, BNSums of y): y = [x_1 | x_2] wc^T + b32 and the sums BatchNorm needs of it, from the same pass."""
+    return _shifted_sums(partial(_streaming_linear, xr, wc, b32), wc.shape[0], xr[0].shape[0], xr[0].device, shard)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -410,54 +413,39 @@ def _fused_bwd() -> bool:
     """sgf_gcn_bn_bwd_dx in the layers' backward.  Off by default: at d = 256 the four workgroups per row tile do not stay
     inside the L2's window on their own (gy / z leave HBM four times) and with the per-tile rendezvous the launch is bound
     by its own serial phases — 2.4-4.4 ms against 2.1 ms for the separate kernels (profiles/r04_bn_bwd_dx_*.md)."""
-    import os
-    return os.environ.get("SGF_GCN_BWD_FUSED", "0") == "1"
+    return _switch("SGF_GCN_BWD_FUSED", False)
 
 
 def _acc_in_place(d: int, dtype) -> bool:
     """sgf_gcn_epilogue_dx2_acc in the layers' backward (default on; SGF_GCN_DX_ACC=0: paired dx2 + one sgf_sum_n)."""
-    import os
-    return (hasattr(K, "gcn_epilogue_dx2_acc_supported") and K.gcn_epilogue_dx2_acc_supported(d, dtype)
-            and os.environ.get("SGF_GCN_DX_ACC", "1") != "0")
+    return _has(K, "gcn_epilogue_dx2_acc_supported", d, dtype) and _switch("SGF_GCN_DX_ACC", True)
 
 
 def gcn_layer_fused_ok(x0: torch.Tensor, w: torch.Tensor) -> bool:
     """bf16 storage, square blocks of 64 / 128 / 256, W = [W1 | W2] — what sgf_gcn_bn_bwd_dx / sgf_gcn_epilogue_cat take."""
-    import os
     d = x0.shape[1] if x0.dim() == 2 else 0
     return (x0.dim() == 2 and x0.shape[0] > 0 and x0.dtype == _BF16 and tuple(w.shape) == (d, 2 * d)
-            and hasattr(K, "gcn_bn_bwd_dx_supported") and K.gcn_bn_bwd_dx_supported(d, x0.dtype)
-            and os.environ.get("SGF_GCN_FUSED", "1") != "0")
+            and _has(K, "gcn_bn_bwd_dx_supported", d, x0.dtype) and _switch("SGF_GCN_FUSED", True))
 
 
 class _LinearBNActRes(torch.autograd.Function):
     """y = A x (already multiplied), x0 -> z = [y | x0] W^T + b -> out = [relu](BatchNorm(z)) [+ x0].
 
-    Forward: one pass for the Linear and BatchNorm's batch sums (sgf_gcn_epilogue_cat), `bn_hook(stats)` — the module's
-    own bookkeeping (batch vs running statistics, running-stat update) — then sgf_bn_apply.
+    Forward: one pass for the Linear and BatchNorm's batch sums (sgf_gcn_epilogue_cat), `book` — the module's own
+    bookkeeping (ours._BNBook: batch vs running statistics, running-stat update) — then sgf_bn_apply.
     Backward: sgf_bn_bwd_stats (the one global reduction), then ONE launch for dz, d y and the running gradient of x0
     (sgf_gcn_bn_bwd_dx), then the weight / bias gradients on sgf_gram."""
 
     @staticmethod
-    def forward(ctx, y, x0, w, b, gamma, beta, bn_hook, relu: bool, use_res: bool, shard, chain, first: bool, pack=None):
+    def forward(ctx, y, x0, w, b, gamma, beta, book, relu: bool, use_res: bool, shard, chain, first: bool, pack=None):
         # pack = {"slot_bytes": S}: the BatchNorm pass also writes `out` in packed form for the next SpMM (pack["out"])
         K.check(y, x0)
         dt = x0.dtype
         wc = w.detach().to(dt).contiguous()
-        b32 = None if b is None else b.detach().float().contiguous()
         yr, xr = _rows16(y), _rows16(x0)
-        want = bn_hook(None)                         # does the BatchNorm normalise with batch statistics?
-        if want:
-            req = {"shard": shard, "out": None, "raw": hasattr(K, "bn_finalize")}
-            z = _linear_with_stats([yr, xr], wc, b32, req)
-            mean, rstd, n_tot, training = bn_hook(req["out"])
-        else:
-            z, _ = _streaming_linear([yr, xr], wc, b32)
-            mean, rstd, n_tot, training = bn_hook(False)
-        g32 = gamma.detach().float().contiguous() if gamma is not None else None
-        be32 = beta.detach().float().contiguous() if beta is not None else None
-        mean = mean.detach().float().contiguous()
-        rstd = rstd.detach().float().contiguous()
+        z, mean, rstd, n_tot, training = _batchnorm_of(book, partial(_streaming_linear, [yr, xr], wc, _f32c(b)), wc.shape[0],
+                                                       yr.shape[0], yr.device, shard)
+        g32, be32 = _f32c(gamma), _f32c(beta)
         if pack is not None:
             out, pack["out"] = K.bn_apply_packed(z, mean, rstd, g32, be32, xr if use_res else None, relu, pack["slot_bytes"])
         else:
@@ -486,8 +474,7 @@ class _LinearBNActRes(torch.autograd.Function):
             # BatchNorm backward, then BOTH input gradients from one HBM read of dz (paired launch); x0's contributions wait
             # in the chain for the one summation pass
             fused_dw = None
-            if (ctx.needs_input_grad[2] and hasattr(K, "gram2_bn_bwd_supported") and _pair_gram()
-                    and K.gram2_bn_bwd_supported(gout, z, yr, xr)):
+            if ctx.needs_input_grad[2] and _pair_gram() and _has(K, "gram2_bn_bwd_supported", gout, z, yr, xr):
                 # dz, dW = dz^T [y | x0] and db from ONE pass over (gout, z): sgf_gram2_bn_bwd (csrc/gramx.hip, k_gramb2)
                 dwf = torch.empty((d, 2 * d), dtype=_F32, device=z.device)
                 dz, dbf = K.gram2_bn_bwd(gout, z, mean, rstd, g32, be32, relu, stats, inv_n, training, yr, xr, dwf[:, :d], dwf[:, d:])
@@ -518,36 +505,41 @@ class _LinearBNActRes(torch.autograd.Function):
         else:
             dw, db = _linear_param_grads(dz, [yr, xr], [d, d], ctx.needs_input_grad[2],
                                          ctx.needs_input_grad[3] and bdt is not None, wdt, bdt)
-        dgamma = stats[d:].to(gdt) if g32 is not None else None
-        dbeta = stats[:d].to(gdt) if be32 is not None else None
-        if shard is not None and g32 is not None:
-            dgamma, dbeta = shard.unsum(dgamma), shard.unsum(dbeta)
+        dgamma, dbeta = _bn_param_grads(stats, d, g32, be32, gdt, shard)
         return dy, dx0, dw, db, dgamma, dbeta, None, None, None, None, None, None, None
 
 
-def linear_bn_act_res(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first, pack=None):
-    return _LinearBNActRes.apply(y, x0, w, b, gamma, beta, bn_hook, relu, use_res, shard, chain, first, pack)
+def linear_bn_act_res(y, x0, w, b, gamma, beta, book, relu, use_res, shard, chain, first, pack=None):
+    return _LinearBNActRes.apply(y, x0, w, b, gamma, beta, book, relu, use_res, shard, chain, first, pack)
+
+
+def _linear(w, b, *xs):
+    return _Linear.apply(w, b, False, None, *xs)[0]
 
 
 def linear(x, w, b):
     """nn.Linear: square bf16 layers / fp32 layers up to 256 wide on the streaming row kernels (sgf_gcn_epilogue_stats / _dx),
     every other shape on sgf_gemm; weight / bias gradients on sgf_gram."""
-    return _Linear.apply(w, b, None, x)
+    return _linear(w, b, x)
 
 
 def linear_bn_stats(xs, w, b, shard=None):
     """(y, (mean, var, n_tot)): nn.Linear of x (or of [x_1 | x_2] for a tuple, GraphConvLayer's use_init) and the
     batch statistics BatchNorm1d needs of its output (large/ours.py:36-40 followed by :87-88) — from the Linear's own
     pass when its blocks are square bf16, else linear + batch_stats."""
-    req = {"shard": shard, "out": None}
-    xs = xs if isinstance(xs, (tuple, list)) else (xs,)
-    y = _Linear.apply(w, b, req, *xs)
-    return y, req["out"]
+    y, stats = _Linear.apply(w, b, True, shard, *(xs if isinstance(xs, (tuple, list)) else (xs,)))
+    return y, stats.moments()
 
 
 def linear_cat(xs, w, b):
     """[x_1 | x_2 | ...] W^T + b without the concatenation (GraphConvLayer with use_init)."""
-    return _Linear.apply(w, b, None, *xs)
+    return _linear(w, b, *xs)
+
+
+def _pad_out_rows(w, b, q: int):
+    """(W, b) with zero rows up to the next multiple of q classes: the caller slices the result, autograd the gradients."""
+    pad = -w.shape[0] % q
+    return F.pad(w, (0, 0, 0, pad)), None if b is None else F.pad(b, (0, pad))
 
 
 def out_linear_cat(xs, w, b):
@@ -558,11 +550,8 @@ def out_linear_cat(xs, w, b):
     m = w.shape[0]
     if (xs[0].dtype == _F32 and xs[0].is_cuda and m % 4 != 0
             and all(K.gcn_epilogue_supported(x.shape[1], (m + 3) // 4 * 4, _F32) for x in xs)):
-        pad = (m + 3) // 4 * 4 - m
-        wp = torch.nn.functional.pad(w, (0, 0, 0, pad))
-        bp = None if b is None else torch.nn.functional.pad(b, (0, pad))
-        return _Linear.apply(wp, bp, None, *xs)[:, :m]
-    return _Linear.apply(w, b, None, *xs)
+        return _linear(*_pad_out_rows(w, b, 4), *xs)[:, :m]
+    return _linear(w, b, *xs)
 
 
 def out_linear(x, w, b):
@@ -572,16 +561,10 @@ def out_linear(x, w, b):
     m = w.shape[0]
     if (x.dtype == _F32 and x.is_cuda and x.dim() == 2 and m % 4 != 0
             and K.gcn_epilogue_supported(w.shape[1], (m + 3) // 4 * 4, _F32)):
-        pad = (m + 3) // 4 * 4 - m
-        wp = torch.nn.functional.pad(w, (0, 0, 0, pad))
-        bp = None if b is None else torch.nn.functional.pad(b, (0, pad))
-        return _Linear.apply(wp, bp, None, x)[:, :m]
+        return _linear(*_pad_out_rows(w, b, 4), x)[:, :m]
     if x.dtype == _BF16 and x.dim() == 2 and m % 8 != 0 and not K.gcn_epilogue_supported(w.shape[1], m, _BF16):
         # bf16 storage and a class count whose rows would not be 16-byte aligned (the 100M recipe: C = 172 -> 344-byte rows):
         # W / b padded with zero rows to the next multiple of 8, so that sgf_gemm stages the logits' gradient with 16-byte
         # loads in the backward (dx = g W) as it stages x in the forward; the result is sliced, autograd slices back
-        pad = (m + 7) // 8 * 8 - m
-        wp = torch.nn.functional.pad(w, (0, 0, 0, pad))
-        bp = None if b is None else torch.nn.functional.pad(b, (0, pad))
-        return _Linear.apply(wp, bp, None, x)[:, :m]
-    return _Linear.apply(w, b, None, x)
+        return _linear(*_pad_out_rows(w, b, 8), x)[:, :m]
+    return _linear(w, b, x)

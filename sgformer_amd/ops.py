@@ -17,13 +17,11 @@ BatchNorm statistics) and all-gather the SpMM operand.
 """
 from __future__ import annotations
 
-import ctypes
-from collections import OrderedDict
 from typing import Optional
 
 import torch
+import torch.nn.functional as F
 
-from . import _lib
 from . import kernels as _kernels
 from .kernels import HipKernels, LONG_ROW, _SEGMENT, _workspace  # noqa: F401  (re-exported: tests, graphed.py)
 from .kernels import _rows, _rows16
@@ -35,6 +33,7 @@ _BF16 = torch.bfloat16
 from . import graph as _graph
 from .graph import *  # noqa: F401,F403,E402
 from .graph import K, graph_cache, _own_block_spmm, _sharded_spmm, _tile_params, _block_shape, _mode  # noqa: F401,E402
+from .linear import _bn_param_grads, _f32c, _has, _switch  # noqa: E402  (linear.py imports nothing of this module)
 
 
 def set_kernels(table):
@@ -331,8 +330,7 @@ class _LNResAct(torch.autograd.Function):
         K.check(x, res, gamma)
         x, res = _rows(x), _rows(res)
         has_ln = gamma is not None
-        g32 = gamma.detach().float().contiguous() if has_ln else None
-        b32 = beta.detach().float().contiguous() if has_ln else None
+        g32, b32 = (_f32c(gamma), _f32c(beta)) if has_ln else (None, None)
         y, mean, rstd = K.ln_fwd(x, res, a, b, g32, b32, relu, eps)
         ctx.save_for_backward(x, res, y if relu else None, g32, mean, rstd)
         ctx.meta = (float(a), float(b), bool(relu), gamma.dtype if has_ln else None)
@@ -362,10 +360,7 @@ class _BNActRes(torch.autograd.Function):
                 shard):
         K.check(x, res)
         x, res = _rows(x), _rows(res)
-        g32 = gamma.detach().float().contiguous() if gamma is not None else None
-        b32 = beta.detach().float().contiguous() if beta is not None else None
-        mean = mean.detach().float().contiguous()
-        rstd = rstd.detach().float().contiguous()
+        g32, b32, mean, rstd = _f32c(gamma), _f32c(beta), _f32c(mean), _f32c(rstd)
         y = K.bn_apply(x, mean, rstd, g32, b32, res, relu)
         ctx.save_for_backward(x, g32, b32, mean, rstd)
         ctx.meta = (bool(relu), bool(training), float(n_tot), shard, res is not None,
@@ -382,11 +377,7 @@ class _BNActRes(torch.autograd.Function):
         if shard is not None:
             shard.all_reduce(stats)  # also makes dgamma / dbeta the global sums
         dx = K.bn_bwd_apply(gy, x, mean, rstd, g32, b32, relu, stats, 1.0 / max(n_tot, 1.0), training)
-        dgamma = stats[d:].to(pdtype) if g32 is not None else None
-        dbeta = stats[:d].to(pdtype) if b32 is not None else None
-        if shard is not None and g32 is not None:
-            # parameter grads are summed over ranks again by ShardContext.sync_grads: pre-divide
-            dgamma, dbeta = shard.unsum(dgamma), shard.unsum(dbeta)
+        dgamma, dbeta = _bn_param_grads(stats, d, g32, b32, pdtype, shard)
         return dx, (gy if has_res else None), dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -658,12 +649,10 @@ class _CombineFC(torch.autograd.Function):
         K.check(x1, x2)
         x1, x2 = _rows16(x1), _rows16(x2)        # sgf_combine_fc_* read 16-byte matrix-core fragments
         ctx.row_map = row_map
-        w32 = w.detach().float().contiguous()
-        b32 = bias.detach().float().contiguous()
+        w32, b32 = _f32c(w), _f32c(bias)
         c = w32.shape[0]
         if (x1.dtype == _F32 or c > 64) and c % 4 != 0:   # the exact-fp32 kernel takes class counts % 4: zero rows, sliced off below
-            w32 = torch.nn.functional.pad(w32, (0, 0, 0, 4 - c % 4))
-            b32 = torch.nn.functional.pad(b32, (0, 4 - c % 4))
+            w32, b32 = F.pad(w32, (0, 0, 0, 4 - c % 4)), F.pad(b32, (0, 4 - c % 4))
         ctx.save_for_backward(x1, x2, w32)
         ctx.meta = (float(a), float(b), w.dtype, bias.dtype, c)
         out = K.combine_fc_fwd(x1, a, x2, b, w32, b32) if row_map is None else K.combine_fc_fwd(x1, a, x2, b, w32, b32, row_map)
@@ -672,37 +661,30 @@ class _CombineFC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x1, x2, w32 = ctx.saved_tensors
-        a, b, wdtype, bdtype, c_true = ctx.meta
+        a, b, wdtype, bdtype, c = ctx.meta
         g = g.float()
         if w32.shape[0] != g.shape[1]:           # fp32 storage: the padded class columns carry a zero gradient
-            g = torch.nn.functional.pad(g, (0, w32.shape[0] - g.shape[1]))
+            g = F.pad(g, (0, w32.shape[0] - g.shape[1]))
         g = g.contiguous()
         row_map = ctx.row_map
-        c = c_true
-        if x1.dtype == _BF16 and hasattr(K, "combine_fc_bwd_g") and g.shape[1] <= 64:
+        if x1.dtype == _BF16 and _has(K, "combine_fc_bwd_g") and g.shape[1] <= 64:
             # the kernel holds the logits' gradient as bf16 matrix-core fragments anyway: it leaves them as the [N, 48]
             # operand of the weight gradient's node reductions (module row order), instead of a cast + a pad pass over g
             dx1, dx2, gp = K.combine_fc_bwd_g(g, w32, a, b, row_map)
-            dw1, db = K.gram(gp, x1, want_colsum=True)
-            dw2, _ = K.gram(gp, x2, want_colsum=False)
-            dw = (a * dw1 + b * dw2)[:c]
-            return dx1, dx2, dw.to(wdtype), db[:c].to(bdtype), None, None, None
-        dx1, dx2 = K.combine_fc_bwd(g, w32, a, b, x1.dtype) if row_map is None else K.combine_fc_bwd(g, w32, a, b, x1.dtype,
-                                                                                                       row_map)
-        # dW = a g^T x1 + b g^T x2, db = colsum(g): node reductions on sgf_gram (g in the activation dtype, its
-        # width padded to a multiple of 4 — the same rounding the unfused path applies to the logits gradient)
-        if row_map is not None:
-            # g is in the CALLER's row order, x1 / x2 in the module's: one gather pass brings g over, cast included
-            gp = K.gather_rows(g, row_map, x1.dtype)
         else:
-            gp = g.to(x1.dtype)
-        if gp.shape[1] % 4 != 0:
-            gp = torch.nn.functional.pad(gp, (0, 4 - gp.shape[1] % 4))
-        gp = _rows(gp)
+            dx1, dx2 = K.combine_fc_bwd(g, w32, a, b, x1.dtype) if row_map is None else K.combine_fc_bwd(g, w32, a, b, x1.dtype,
+                                                                                                           row_map)
+            # g in the activation dtype, its width padded to a multiple of 4 — the same rounding the unfused path applies to
+            # the logits gradient.  With a row map g is in the CALLER's row order, x1 / x2 in the module's: one gather pass
+            # brings g over, cast included
+            gp = K.gather_rows(g, row_map, x1.dtype) if row_map is not None else g.to(x1.dtype)
+            if gp.shape[1] % 4 != 0:
+                gp = F.pad(gp, (0, 4 - gp.shape[1] % 4))
+            gp = _rows(gp)
+        # dW = a gp^T x1 + b gp^T x2, db = colsum(gp): node reductions on sgf_gram
         dw1, db = K.gram(gp, x1, want_colsum=True)
         dw2, _ = K.gram(gp, x2, want_colsum=False)
-        dw = (a * dw1 + b * dw2)[:c]
-        return dx1, dx2, dw.to(wdtype), db[:c].to(bdtype), None, None, None
+        return dx1, dx2, (a * dw1 + b * dw2)[:c].to(wdtype), db[:c].to(bdtype), None, None, None
 
 
 def combine_fc(x1, x2, w, bias, a: float, b: float, row_map=None) -> torch.Tensor:
@@ -714,14 +696,12 @@ def combine_fc(x1, x2, w, bias, a: float, b: float, row_map=None) -> torch.Tenso
 
 
 def combine_fc_mapped_supported(x: torch.Tensor, classes: int) -> bool:
-    import os
-    return (x.dim() == 2 and hasattr(K, "combine_fc_mapped_supported") and os.environ.get("SGF_HEAD_MAPPED", "1") != "0"
-            and K.combine_fc_mapped_supported(x.shape[1], classes, x.dtype))
+    return (x.dim() == 2 and _switch("SGF_HEAD_MAPPED", True)
+            and _has(K, "combine_fc_mapped_supported", x.shape[1], classes, x.dtype))
 
 
 def combine_fc_supported(x: torch.Tensor, classes: int) -> bool:
-    import os
-    if x.dim() == 2 and x.dtype == _BF16 and classes > 64 and os.environ.get("SGF_HEAD_WIDE", "0") != "1":
+    if x.dim() == 2 and x.dtype == _BF16 and classes > 64 and not _switch("SGF_HEAD_WIDE", False):
         # bf16 storage with more than 64 classes: sgf_combine_fc_* would run on the exact-fp32 matrix cores (157 TF, padded
         # to 256 x 256) and is compute-bound there — measured on the 100M recipe (d = 128, C = 172, N = 13.9 M): 18.5 + 16.3 ms
         # per step against ~12 ms for sgf_axpby + the bf16 streaming Linear, 251.9 vs 234.6 ms per step.  The logits

@@ -27,6 +27,9 @@ GPU only: a CPU tensor raises (no eager fallback by design).
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+from typing import Optional
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -152,9 +155,68 @@ def _attention_matrix(qs, ks):
     return attention / normalizer
 
 
-def _uses_batch_stats(module: nn.Module, bn: nn.BatchNorm1d) -> bool:
-    """nn.BatchNorm1d's rule for normalising with batch (not running) statistics."""
-    return module.training or not bn.track_running_stats or bn.running_mean is None
+class _BNBook:
+    """nn.BatchNorm1d's bookkeeping for one call of `bn` inside `module` (whose train / eval mode decides): which statistics
+    normalise, the count check, and the update of the running statistics.  The statistics themselves come from the kernels;
+    every method that answers with statistics returns (mean, rstd, count, used batch statistics)."""
+
+    def __init__(self, module: nn.Module, bn: nn.BatchNorm1d):
+        self.module, self.bn = module, bn
+
+    def use_batch(self) -> bool:
+        """nn.BatchNorm1d's rule for normalising with batch (not running) statistics."""
+        bn = self.bn
+        return self.module.training or not bn.track_running_stats or bn.running_mean is None
+
+    def _tracks(self, count: float) -> bool:
+        """Does this call update the running statistics?  (Raises for a batch BatchNorm1d refuses to train on.)"""
+        if count <= 1 and self.module.training:
+            raise ValueError("Expected more than 1 value per channel when training")
+        bn = self.bn
+        return self.module.training and bn.track_running_stats and bn.running_mean is not None
+
+    def from_sums(self, stats):
+        """Batch statistics as the statistics pass left them (ops.BNSums): mean, rstd and the running update in ONE launch
+        (K.bn_finalize) unless the update is a cumulative average (momentum None) or the buffers are not fp32."""
+        bn = self.bn
+        track = self._tracks(stats.count)
+        if ops._has(ops.K, "bn_finalize") and (not track or (bn.momentum is not None and bn.running_mean.dtype == torch.float32)):
+            with torch.no_grad():
+                if track:
+                    bn.num_batches_tracked += 1
+                mean, rstd = ops.K.bn_finalize(stats.sums, stats.shift, stats.count, bn.eps,
+                                               float(bn.momentum) if track else 0.0,
+                                               bn.running_mean if track else None, bn.running_var if track else None)
+            return mean, rstd, stats.count, True
+        return self.from_moments(*stats.moments())
+
+    def from_moments(self, mean, var, count):
+        """Batch statistics given as (mean, biased variance, count)."""
+        bn = self.bn
+        if self._tracks(count):
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+                m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+                bn.running_mean.mul_(1.0 - m).add_(mean.to(bn.running_mean.dtype), alpha=m)
+                unbiased = var * (count / max(count - 1.0, 1.0))
+                bn.running_var.mul_(1.0 - m).add_(unbiased.to(bn.running_var.dtype), alpha=m)
+        return mean, torch.rsqrt(var + bn.eps), count, True
+
+    def running(self, count: float = 0.0):
+        """The running statistics; `count` is handed on (the backward of a BatchNorm in eval mode does not use it)."""
+        bn = self.bn
+        return bn.running_mean.float(), torch.rsqrt(bn.running_var.float() + bn.eps), count, False
+
+
+@dataclass
+class _Stems:
+    """What SGFormer._core hands the two branches when it has run their first Linear layers in one pass over x."""
+    trans: torch.Tensor                            # TransConv's fcs[0](x) ...
+    trans_normed: bool = False                     # ... with LayerNorm + relu already applied (ops.stem_pair_bn)
+    gcn: Optional[torch.Tensor] = None             # GraphConv's fcs[0](x): before its BatchNorm, with
+    gcn_stats: Optional[tuple] = None              # (mean, var, count) for it or None — or, when gcn_first is set,
+    gcn_first: Optional[torch.Tensor] = None       # after BatchNorm + relu, this second alias feeding the first SpMM
+    pack: Optional[dict] = None                    # the pack request of the stem node (GraphConv.pack_request)
 
 
 class GraphConvLayer(nn.Module):
@@ -237,66 +299,16 @@ class GraphConv(nn.Module):
     def _bn_act_res(self, bn: nn.BatchNorm1d, x, res, relu, stats=None):
         """[relu](BatchNorm1d(x)) [+ res] with nn.BatchNorm1d's train/eval + running-stat rules.
         `stats`: (mean, var, count) of x if its producer already accumulated them."""
-        shard = self._shard
-        use_batch = _uses_batch_stats(self, bn)
-        if use_batch:
-            mean, var, n_tot = stats if stats is not None else ops.batch_stats(x, shard)
-            if n_tot <= 1 and self.training:
-                raise ValueError("Expected more than 1 value per channel when training")
-            if self.training and bn.track_running_stats and bn.running_mean is not None:
-                with torch.no_grad():
-                    bn.num_batches_tracked += 1
-                    m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                    bn.running_mean.mul_(1.0 - m).add_(mean.to(bn.running_mean.dtype), alpha=m)
-                    unbiased = var * (n_tot / max(n_tot - 1.0, 1.0))
-                    bn.running_var.mul_(1.0 - m).add_(unbiased.to(bn.running_var.dtype), alpha=m)
+        shard, book = self._shard, _BNBook(self, bn)
+        if book.use_batch():
+            mean, rstd, n_tot, used = book.from_moments(*(stats if stats is not None else ops.batch_stats(x, shard)))
         else:
-            mean, var, n_tot = bn.running_mean.float(), bn.running_var.float(), float(x.shape[0])
-        rstd = torch.rsqrt(var + bn.eps)
-        return ops.bn_act_res(x, res, bn.weight, bn.bias, mean, rstd, relu, use_batch, n_tot, shard)
+            mean, rstd, n_tot, used = book.running(float(x.shape[0]))
+        return ops.bn_act_res(x, res, bn.weight, bn.bias, mean, rstd, relu, used, n_tot, shard)
 
-    def _bn_hook(self, bn: nn.BatchNorm1d):
-        """nn.BatchNorm1d's bookkeeping as a callback for ops.linear_bn_act_res: hook(None) -> does this call normalise with
-        batch statistics?; hook((mean, var, count)) / hook(False) -> (mean, rstd, count, used batch statistics), updating
-        the running statistics exactly as _bn_act_res does."""
-        def hook(stats):
-            use_batch = _uses_batch_stats(self, bn)
-            if stats is None:
-                return use_batch
-            if use_batch and stats[0] == "raw":
-                # (sums, shift, count) as the statistics pass left them: mean, rstd and the running update in ONE launch
-                _, sums, shift, n_tot = stats
-                if n_tot <= 1 and self.training:
-                    raise ValueError("Expected more than 1 value per channel when training")
-                track = self.training and bn.track_running_stats and bn.running_mean is not None
-                if track and bn.momentum is not None and bn.running_mean.dtype == torch.float32:
-                    with torch.no_grad():
-                        bn.num_batches_tracked += 1
-                        mean, rstd = ops.K.bn_finalize(sums, shift, n_tot, bn.eps, float(bn.momentum), bn.running_mean,
-                                                       bn.running_var)
-                    return mean, rstd, n_tot, True
-                if not track:
-                    mean, rstd = ops.K.bn_finalize(sums, shift, n_tot, bn.eps, 0.0, None, None)
-                    return mean, rstd, n_tot, True
-                d = sums.numel() // 2                    # cumulative moving average (momentum None) / non-fp32 buffers
-                m1 = sums[:d] / max(n_tot, 1.0)
-                stats = ((shift + m1) if shift is not None else m1, (sums[d:] / max(n_tot, 1.0) - m1 * m1).clamp_min_(0.0),
-                         n_tot)
-            if use_batch:
-                mean, var, n_tot = stats
-                if n_tot <= 1 and self.training:
-                    raise ValueError("Expected more than 1 value per channel when training")
-                if self.training and bn.track_running_stats and bn.running_mean is not None:
-                    with torch.no_grad():
-                        bn.num_batches_tracked += 1
-                        m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                        bn.running_mean.mul_(1.0 - m).add_(mean.to(bn.running_mean.dtype), alpha=m)
-                        unbiased = var * (n_tot / max(n_tot - 1.0, 1.0))
-                        bn.running_var.mul_(1.0 - m).add_(unbiased.to(bn.running_var.dtype), alpha=m)
-            else:
-                mean, var, n_tot = bn.running_mean.float(), bn.running_var.float(), 0.0
-            return mean, torch.rsqrt(var + bn.eps), n_tot, use_batch
-        return hook
+    @property
+    def _drop_on(self) -> bool:
+        return self.training and self.dropout is not None and self.dropout > 0.0
 
     def pack_request(self, layer: int, n: int, dtype, edge_index):
         """{"slot_bytes": S} if the SpMM of layer `layer` (0-based) should gather a packed copy of its operand — handed to
@@ -305,8 +317,7 @@ class GraphConv(nn.Module):
         bf16 [n, 256] on one GPU with dropout inactive, and the launch the wave-per-row kernel
         (ops.spmm_packed_slot).  Full-graph steps only: never inside a stream capture."""
         slot = PACKED_SLOT_BYTES[layer] if layer < len(PACKED_SLOT_BYTES) else 0
-        drop_on = self.training and self.dropout is not None and self.dropout > 0.0
-        if (not slot or drop_on or self._shard is not None or ops.K.name != "hip" or layer >= len(self.convs)
+        if (not slot or self._drop_on or self._shard is not None or ops.K.name != "hip" or layer >= len(self.convs)
                 or self.convs[layer]._shard is not None or torch.cuda.is_current_stream_capturing()):
             return None
         if isinstance(edge_index, ops.CSRGraph):
@@ -322,26 +333,22 @@ class GraphConv(nn.Module):
     def fused_stem_ok(self, x) -> bool:
         """SGFormer.forward may run this branch's stem Linear + BatchNorm + relu (and TransConv's stem Linear) as ONE
         autograd node (ops.stem_pair_bn) when the layers behind it are the fused ones and no dropout follows the stem."""
-        import os
         d = self.fcs[0].out_features
-        drop_on = self.training and self.dropout is not None and self.dropout > 0.0
-        return (self.use_bn and not drop_on and len(self.convs) > 0 and all(c.use_init for c in self.convs)
+        return (self.use_bn and not self._drop_on and len(self.convs) > 0 and all(c.use_init for c in self.convs)
                 and x.dim() == 2 and x.dtype == torch.bfloat16
                 and all(tuple(c.W.weight.shape) == (d, 2 * d) for c in self.convs)
-                and hasattr(ops.K, "gcn_bn_bwd_dx_supported") and ops.K.gcn_bn_bwd_dx_supported(d, x.dtype)
-                and os.environ.get("SGF_GCN_FUSED", "1") != "0" and os.environ.get("SGF_STEM_FUSED", "1") != "0")
+                and ops._has(ops.K, "gcn_bn_bwd_dx_supported", d, x.dtype)
+                and ops._switch("SGF_GCN_FUSED", True) and ops._switch("SGF_STEM_FUSED", True))
 
     def _fused_layers(self, x0):
         """The products / pokec / papers100M recipes (use_init, BatchNorm, no active dropout, bf16 rows of 64 / 128 / 256):
         every layer's Linear + BatchNorm + activation + residual is ONE autograd node (ops.linear_bn_act_res)."""
-        drop_on = self.training and self.dropout is not None and self.dropout > 0.0
-        return (self.use_bn and not drop_on and len(self.convs) > 0 and all(c.use_init for c in self.convs)
+        return (self.use_bn and not self._drop_on and len(self.convs) > 0 and all(c.use_init for c in self.convs)
                 and all(ops.gcn_layer_fused_ok(x0, c.W.weight) for c in self.convs))
 
     def _stage(self, bn, x, res, relu, stats=None):
         """BN -> act -> dropout -> + res, fused into one pass whenever dropout is inactive."""
-        drop_on = self.training and self.dropout is not None and self.dropout > 0.0
-        fuse_res = res is not None and not drop_on
+        fuse_res = res is not None and not self._drop_on
         if self.use_bn:
             x = self._bn_act_res(bn, x, res if fuse_res else None, relu, stats)
         else:
@@ -354,20 +361,19 @@ class GraphConv(nn.Module):
 
     def forward(self, x, edge_index, stem=None):
         """edge_index: the int64 [2, nnz] tensor of the reference, or an ops.CSRGraph built from it.
-        `stem` (not in the reference signature): (fcs[0](x), its batch statistics or None), when SGFormer.forward
-        has computed both branches' first Linear in one pass over x (ops.stem_pair)."""
+        `stem` (not in the reference signature): a _Stems, when SGFormer.forward has computed both branches' first Linear
+        in one pass over x (ops.stem_pair / ops.stem_pair_bn)."""
         ops._require_cuda(x, None if isinstance(edge_index, ops.CSRGraph) else edge_index)
         x_first = packed = None
-        if stem is not None and len(stem) >= 3:
-            # ("bn", x0, x0'[, pack request]): the stem ran as one node with its BatchNorm (ops.stem_pair_bn); x0' feeds the
-            # first SpMM — from its packed copy when the node was asked for one (pack_request: the copy is in ["out"])
-            x, x_first = stem[1], stem[2]
-            # (taken OUT of the request: the copy, 0.94 GB at products size, lives until the first SpMM has read it, not
-            # until the forward returns)
-            packed = stem[3].pop("out", None) if len(stem) > 3 and stem[3] is not None else None
+        if stem is not None and stem.gcn_first is not None:
+            # the stem ran as one node with its BatchNorm (ops.stem_pair_bn); its second alias feeds the first SpMM — from
+            # its packed copy when the node was asked for one (pack_request: the copy is in ["out"], and is taken OUT of the
+            # request: 0.94 GB at products size, it lives until the first SpMM has read it, not until the forward returns)
+            x, x_first = stem.gcn, stem.gcn_first
+            packed = stem.pack.pop("out", None) if stem.pack is not None else None
         else:
             if stem is not None:
-                x, stats0 = stem
+                x, stats0 = stem.gcn, stem.gcn_stats
             else:
                 x, stats0 = _lin(x, self.fcs[0]), None
             x = self._stage(self.bns[0], x, None, True, stats0)
@@ -382,7 +388,7 @@ class GraphConv(nn.Module):
                 packed = None
                 # this layer's BatchNorm pass writes the next SpMM's operand: packed too, if that launch gathers it
                 req = self.pack_request(i + 1, x0.shape[0], x0.dtype, edge_index) if self.use_act else None
-                x = ops.linear_bn_act_res(y, x0, conv.W.weight, conv.W.bias, bn.weight, bn.bias, self._bn_hook(bn),
+                x = ops.linear_bn_act_res(y, x0, conv.W.weight, conv.W.bias, bn.weight, bn.bias, _BNBook(self, bn),
                                           self.use_act, self.use_residual, self._shard, chain, i == 0, req)
                 packed = req.pop("out", None) if req is not None else None
             return x
@@ -394,7 +400,7 @@ class GraphConv(nn.Module):
         hub = list(ops.fan_out(x, k)) if k <= 8 else [x] * k
         x = hub.pop()
         for i, conv in enumerate(self.convs):
-            want = self.use_bn and _uses_batch_stats(self, self.bns[i + 1])
+            want = self.use_bn and _BNBook(self, self.bns[i + 1]).use_batch()
             x0 = hub.pop() if uses_init[i] else None
             if want:    # the conv's Linear accumulates the statistics its BatchNorm needs in the same pass
                 x, stats = conv(x, edge_index, x0, bn_stats=True)
@@ -510,14 +516,14 @@ class TransConv(nn.Module):
         return ops.ln_res_act(x, res, a, b, gamma, beta, relu, ln.eps)
 
     def _embed(self, x, training, stem=None):
-        if isinstance(stem, tuple) and stem[0] == "ln":      # Linear + LayerNorm + relu already applied (ops.stem_pair_bn)
-            return _drop(stem[1], self.dropout, training)
-        x = _lin(x, self.fcs[0]) if stem is None else stem
+        if stem is not None and stem.trans_normed:           # Linear + LayerNorm + relu already applied (ops.stem_pair_bn)
+            return _drop(stem.trans, self.dropout, training)
+        x = _lin(x, self.fcs[0]) if stem is None else stem.trans
         x = self._ln(self.bns[0], x, None, 1.0, 0.0, True)
         return _drop(x, self.dropout, training)
 
     def forward(self, x, stem=None):
-        """`stem` (not in the reference signature): fcs[0](x) when SGFormer.forward already has it (ops.stem_pair)."""
+        """`stem` (not in the reference signature): a _Stems when SGFormer.forward already has fcs[0](x) (ops.stem_pair)."""
         ops._require_cuda(x)
         x = self._embed(x, self.training, stem)
         layer_ = [x]
@@ -649,7 +655,7 @@ class SGFormer(nn.Module):
         perm = view.perm if view is not None else None
         f = x.shape[1]
         fp = _entry_width(f, cdt)
-        pad = fp != f and not x.requires_grad and hasattr(ops.K, "pad_rows")
+        pad = fp != f and not x.requires_grad and ops._has(ops.K, "pad_rows")
         if x.requires_grad:
             if perm is not None:
                 x = ops.permute_rows(x, view.perm, view.inv, cdt)
@@ -678,7 +684,7 @@ class SGFormer(nn.Module):
         storage cast in one pass — the captured step of sgformer_amd.graphed calls this inside its graph."""
         f = x.shape[1]
         fp = _entry_width(f, cdt)
-        if fp != f and hasattr(ops.K, "pad_rows"):
+        if fp != f and ops._has(ops.K, "pad_rows"):
             return ops.K.pad_rows(x, None, fp, cdt)
         return x if x.dtype == cdt else x.to(cdt)
 
@@ -687,7 +693,7 @@ class SGFormer(nn.Module):
         `edge_index`: the reference's tensor, or an object with the CSR arrays (ops.CSRGraph, graphed.StaticCSR)."""
         # K10: the first Linear of both branches reads the same x — one pass, two outputs, the GCN stem's BatchNorm
         # sums on the way (bf16 storage, <= 128 input features)
-        stem_t = stem_g = None
+        stem = None
         gc, tc = (self.graph_conv if self.use_graph else None), self.trans_conv
         both = gc is not None and hasattr(tc, "fcs") and hasattr(gc, "fcs") and hasattr(gc, "bns")
         wg, wt = (_stem_w(gc.fcs[0], x), _stem_w(tc.fcs[0], x)) if both else (None, None)
@@ -699,13 +705,20 @@ class SGFormer(nn.Module):
                 ln = (tc.bns[0].weight, tc.bns[0].bias, tc.bns[0].eps, True)
             req = gc.pack_request(0, x.shape[0], x.dtype, edge_index)
             x0a, x0b, yt = ops.stem_pair_bn(x, wg, gc.fcs[0].bias, wt, tc.fcs[0].bias,
-                                            bn0.weight, bn0.bias, gc._bn_hook(bn0), gc._shard, ln, req)
-            stem_t, stem_g = (("ln", yt) if ln is not None else yt), ("bn", x0a, x0b, req)
+                                            bn0.weight, bn0.bias, _BNBook(gc, bn0), gc._shard, ln, req)
+            stem = _Stems(trans=yt, trans_normed=ln is not None, gcn=x0a, gcn_first=x0b, pack=req)
         elif both and ops.stem_pair_supported(x, wg, wt):
-            want = gc.use_bn and _uses_batch_stats(gc, gc.bns[0])
+            want = gc.use_bn and _BNBook(gc, gc.bns[0]).use_batch()
             (yg, yt), st = ops.stem_pair(x, wg, gc.fcs[0].bias, wt, tc.fcs[0].bias,
                                          want_stats0=want, shard=gc._shard)
-            stem_t, stem_g = yt, (yg, st)
+            stem = _Stems(trans=yt, gcn=yg, gcn_stats=st)
+
+        def trans_branch():
+            return self.trans_conv(x) if stem is None else self.trans_conv(x, stem=stem)
+
+        def graph_branch():
+            return self.graph_conv(x, edge_index) if stem is None else self.graph_conv(x, edge_index, stem=stem)
+
         if (self.use_graph and self.overlap_branches and ops.K.name == "hip" and self.graph_conv._shard is None
                 and x.shape[0] >= OVERLAP_MIN_NODES and not torch.cuda.is_current_stream_capturing() and not ops._fused_bwd()):
             # The two branches are independent until the combine: run the attention branch on a side
@@ -715,20 +728,16 @@ class SGFormer(nn.Module):
             side = _side_stream(x.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                x1 = self.trans_conv(x) if stem_t is None else self.trans_conv(x, stem=stem_t)
+                x1 = trans_branch()
             x.record_stream(side)
-            for t in (stem_t if isinstance(stem_t, (tuple, list)) else (stem_t,)):
-                if torch.is_tensor(t):
-                    t.record_stream(side)
-            x2 = self.graph_conv(x, edge_index) if stem_g is None else self.graph_conv(x, edge_index, stem=stem_g)
+            if stem is not None:
+                stem.trans.record_stream(side)
+            x2 = graph_branch()
             cur.wait_stream(side)
             x1.record_stream(cur)
         else:
-            x1 = self.trans_conv(x) if stem_t is None else self.trans_conv(x, stem=stem_t)
-            if self.use_graph:
-                x2 = self.graph_conv(x, edge_index) if stem_g is None else self.graph_conv(x, edge_index, stem=stem_g)
-            else:
-                x2 = None
+            x1 = trans_branch()
+            x2 = graph_branch() if self.use_graph else None
         if self.use_graph and self.aggregate == 'add' and ops.combine_fc_supported(x1, self.fc.out_features):
             # gw * x2 + (1 - gw) * x1 -> fc in ONE kernel (large/ours.py:269-270,275): the combined
             # activations are never written, the logits come out in fp32

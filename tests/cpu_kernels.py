@@ -72,6 +72,14 @@ class CpuKernels:
         dx = g.to(dtype).float() @ w.to(dtype).float()
         return (a * dx).to(dtype), (b * dx).to(dtype)
 
+    @staticmethod
+    def combine_fc_bwd_g(g, w, a, b, row_map=None):
+        # combine_fc_bwd in bf16 plus gp: the logits' gradient in bf16, zero-padded to 16 columns, module row order
+        dx1, dx2 = CpuKernels.combine_fc_bwd(g, w, a, b, torch.bfloat16, row_map)
+        gm = g if row_map is None else g[row_map.long()]
+        gp = torch.nn.functional.pad(gm.to(torch.bfloat16), (0, -g.shape[1] % 16))
+        return dx1, dx2, gp
+
     # ---- streaming row-GEMM (csrc/rowgemm.hip) ----
     @staticmethod
     def gcn_epilogue_supported(d_in, d_out, dtype):
@@ -500,6 +508,16 @@ class CpuKernels:
         g = gy.float() if gy2 is None else (gy.float() + gy2.float())
         dz = CpuKernels.bn_bwd_apply(g, z, mean, rstd, gamma, beta, relu, stats, inv_n, training).float()
         return dz.t() @ b.float(), dz.sum(0)
+
+    @staticmethod
+    def gram2_bn_bwd_supported(g, z, b1, b2):
+        return (all(t.dtype == torch.bfloat16 and t.dim() == 2 for t in (g, z, b1, b2)) and b1.shape == b2.shape
+                and g.shape == z.shape and z.shape[1] in (64, 128, 256) and b1.shape[1] == z.shape[1])
+
+    @staticmethod
+    def gram2_bn_bwd(g, z, mean, rstd, gamma, beta, relu, stats, inv_n, training, b1, b2, out1, out2):
+        dz = CpuKernels.bn_bwd_apply(g, z, mean, rstd, gamma, beta, relu, stats, inv_n, training)
+        return dz, CpuKernels.gram2(dz, b1, b2, out1, out2, want_colsum=True)
 
     @staticmethod
     def bn_bwd_apply(gy, x, mean, rstd, gamma, beta, relu, stats, inv_n, training):
