@@ -39,7 +39,7 @@ def main():
     xi = x[idx.to(dev)]
     nnz = int(ei_i.shape[1])
     graph = graphed.StaticCSR(m, nnz + 1024, dev, 0)
-    graph.load(*ei_i._sgf_csr[:3])
+    graph.load(*ops.hints_of(ei_i).csr[:3])
     xc = model._entry_copy_uncached(xi, torch.bfloat16)
     h = torch.randn(m, d, device=dev).bfloat16().requires_grad_(True)
     h2 = torch.randn(m, d, device=dev).bfloat16().requires_grad_(True)

@@ -13,6 +13,7 @@ unchanged.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 from typing import Optional
 
@@ -68,11 +69,6 @@ def _parent_of(edge_index: torch.Tensor, ei_dev: torch.Tensor, n: int) -> _Paren
     return p
 
 
-def _use_parent_csr() -> bool:
-    import os
-    return hasattr(ops.K, "subgraph_csr") and os.environ.get("SGF_SUBGRAPH_CSR", "1") != "0"
-
-
 def subgraph(subset, edge_index, edge_attr=None, relabel_nodes: bool = False, num_nodes: Optional[int] = None):
     """torch_geometric.utils.subgraph — see _subgraph.  On the GPU the whole call (the index's H2D copy, the kernels, the one
     device -> host read of the edge count) runs on the PREP stream (sgformer_amd/staging.py): the host read then waits for
@@ -82,7 +78,7 @@ def subgraph(subset, edge_index, edge_attr=None, relabel_nodes: bool = False, nu
         dev = edge_index.device if edge_index.is_cuda else torch.device("cuda", torch.cuda.current_device())
         with staging.on_prep(dev) as hand_over:
             out, attr = _subgraph(subset, edge_index, edge_attr, relabel_nodes, num_nodes)
-            hand_over(out, attr, *(getattr(out, "_sgf_csr", None) or ()))
+            hand_over(out, attr, *(ops.hints_of(out).csr or ()))
         return out, attr
     return _subgraph(subset, edge_index, edge_attr, relabel_nodes, num_nodes)
 
@@ -93,36 +89,29 @@ def _subgraph(subset, edge_index, edge_attr=None, relabel_nodes: bool = False,
 
     relabel_nodes=True without edge attributes — the mini-batch trainer's call (large/main-batch.py:139) — takes the parent's
     cached CSR (sgf_subgraph_csr_*): the batch's m parent rows are read instead of all parent edges, and the result carries its
-    normalised CSR (`_sgf_csr`, adopted by ops.CSRGraph instead of a second sort) and, for a parent with A^T == A, the promise
-    that it is symmetric too.  Its edges come in (target, source) order — the same multiset as the reference's, whose order
+    normalised CSR (ops.EdgeHints.csr, adopted by ops.CSRGraph instead of a second sort) and, for a parent with A^T == A, the
+    promise that it is symmetric too.  Its edges come in (target, source) order — the same multiset as the reference's, whose order
     (the parent's edge order) nothing on the path depends on; SGF_SUBGRAPH_CSR=0 keeps the edge-order-preserving passes."""
-    if ops.K.name == "hip":
-        if not torch.cuda.is_available():
-            ops.K.check(edge_index)   # raises the standard no-CPU-path error
-        device = edge_index.device if edge_index.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    else:
-        device = edge_index.device
-    n = int(num_nodes) if num_nodes is not None else (int(edge_index.max()) + 1 if edge_index.numel() else 0)
+    device, n = _device_for(edge_index), _nodes(edge_index, num_nodes)
     if isinstance(subset, (list, tuple)):
         subset = torch.tensor(subset, dtype=torch.long)
     subset = subset.to(device)
     if subset.dtype == torch.bool:
         subset = subset.nonzero().view(-1)
     ei = _on_gpu(edge_index, device) if ops.K.name == "hip" else edge_index
-    if relabel_nodes and edge_attr is None and _use_parent_csr() and ei.shape[1] > 0:
+    if (relabel_nodes and edge_attr is None and ops._has(ops.K, "subgraph_csr")
+            and os.environ.get("SGF_SUBGRAPH_CSR", "1") != "0" and ei.shape[1] > 0):
         parent = _parent_of(edge_index, ei, n)
         sub = subset.contiguous().long()
         got = ops.K.subgraph_csr(parent.rowptr, parent.colind, n, sub, parent.local_of, True)
         if got is not None:
             rowptr_b, colind_b, val_b, deg_b, out, longest = got
-            out._sgf_trusted = True
-            out._sgf_max_in_degree = longest              # (read with the batch's size: no long-row path for most batches)
-            out._sgf_csr = (rowptr_b, colind_b, val_b, deg_b)
-            out._sgf_symmetric = parent.symmetric
-            return out, None
+            # (`longest` is read with the batch's size: no long-row path for most batches)
+            return ops.EdgeHints(trusted=True, max_in_degree=longest, csr=(rowptr_b, colind_b, val_b, deg_b),
+                                 symmetric=parent.symmetric).attach(out), None
     out, eid = ops.K.subgraph(ei, n, subset.contiguous().long(), bool(relabel_nodes), edge_attr is not None)
     if relabel_nodes:
-        out._sgf_trusted = True       # ids are positions in `subset`: CSRGraph skips its range check (a host sync)
+        ops.EdgeHints(trusted=True).attach(out)     # ids are positions in `subset`: CSRGraph skips its range check (a host sync)
     if edge_attr is not None:
         edge_attr = edge_attr.to(device)[eid]
     return out, edge_attr

@@ -68,6 +68,7 @@ class HaloPlan:
 
     def __init__(self, colind: torch.Tensor, ctx: "ShardContext"):
         dev = colind.device
+        self.own_tile_plan = None       # ops._own_block_spmm: the TilePlan of the own-column block (False: not worth one)
         cols = torch.unique(colind.long())                      # sorted
         remote = cols[(cols < ctx.r0) | (cols >= ctx.r1)]
         self.n_halo = int(remote.numel())
@@ -116,7 +117,7 @@ class HaloPlan:
         return self._split
 
 
-class ShardedGraph:
+class ShardedGraph(ops.GraphOperand):
     """Local row block of the normalised adjacency (and of its transpose) with global column ids.
 
     Two ways in.  Default: every rank holds the GLOBAL edge_index; the block is cut out of the full
@@ -126,6 +127,7 @@ class ShardedGraph:
     Column ids address the all-gathered operand, whose row g is global node g."""
 
     def __init__(self, edge_index: torch.Tensor, ctx: "ShardContext"):
+        super().__init__()
         self.n = ctx.n_max * ctx.world          # rows of the gathered operand
         self.n_local = ctx.n_local
         if ctx.local_edges:
@@ -226,24 +228,15 @@ class ShardedGraph:
         self._t = (self.rowptr, self.colind, self.val)
         self.t_long_segments = self.long_segments
 
-    @staticmethod
-    def _slice(rowptr, colind, val, ctx):
-        lo, hi = int(rowptr[ctx.r0]), int(rowptr[ctx.r1])
-        return ((rowptr[ctx.r0:ctx.r1 + 1] - lo).contiguous(), colind[lo:hi].clone(),
-                val[lo:hi].clone())
-
     def transposed(self):
         return self._t
 
     def halo(self, ctx: "ShardContext", transposed: bool):
         """HaloPlan of the forward block (or of the A^T block the backward multiplies with); the same plan
         when A is symmetric.  Built on first use — by every rank at the same point of the step."""
-        if not hasattr(self, "_halo"):
-            self._halo = {}
-        key = bool(transposed) and not self.symmetric
+        key = self._stored(transposed)
         if key not in self._halo:
-            colind = self._t[1] if key else self.colind
-            self._halo[key] = HaloPlan(colind, ctx)
+            self._halo[key] = HaloPlan(self.arrays(key)[1], ctx)
         return self._halo[key]
 
 
@@ -360,14 +353,13 @@ class Repartition:
             return
         ei2 = torch.stack([new_src, new_dst])
         del new_src, new_dst, mine, cols
-        ei2._sgf_trusted = True
         graph = ShardedGraph(ei2, ctx)
         # the rows of this rank follow the communities: its own-column block has the locality the re-ordered single-GPU
         # graph has — stream / tile kernels instead of the plain row kernel (ops._own_block_spmm)
         graph.locality = True
         graph.comm_local = comm_new[ctx.r0:ctx.r1].contiguous()
-        self.edge_index, self.graph = ei2, graph
-        ei2._sgf_sharded_graph = graph
+        self.graph = graph
+        self.edge_index = ops.EdgeHints(trusted=True, sharded_graph=graph).attach(ei2)
         self.perm, self.inv = perm, inv
         self.plan = RowExchange(perm[ctx.r0:ctx.r1], ctx)        # new row p of this rank = old node perm[p]
         self._cache = None
@@ -390,6 +382,9 @@ class Repartition:
 
 class ShardContext:
     """Partition + collectives of one rank.  `group=None` uses the default process group."""
+    overlap = False                  # multiply the own-column entries while the halo rows are on the links (ops._sharded_spmm)
+    overlapped_exchanges = 0         # ... and how often that happened
+    _repart = (None, None, None)     # (key, Repartition or None, the pinned edge list) of the last repartition_for
 
     def __init__(self, n_global: int, group=None, local_edges: bool = False):
         """local_edges=True: `model(x_local, edge_index)` receives only the edges whose target this
@@ -447,15 +442,13 @@ class ShardContext:
     def repartition_for(self, edge_index: torch.Tensor):
         """The Repartition of this (replicated) edge list, or None when disabled / not adopted; decided once per
         edge_index, at the same point of the step on every rank."""
-        if not self.reorder or not hasattr(ops.K, "reorder"):
+        if not self.reorder or not ops._has(ops.K, "reorder"):
             return None
-        cache = self.__dict__.setdefault("_repart", {})
         key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape))
-        if key not in cache:
-            cache.clear()
+        if self._repart[0] != key:
             rp = Repartition(edge_index, self)
-            cache[key] = (rp if rp.adopted else None, edge_index)
-        return cache[key][0]
+            self._repart = (key, rp if rp.adopted else None, edge_index)
+        return self._repart[1]
 
     # ---- partition helpers ----
     def shard_rows(self, t: torch.Tensor) -> torch.Tensor:
@@ -466,7 +459,7 @@ class ShardContext:
         return global_idx[m] - self.r0
 
     def graph_for(self, edge_index: torch.Tensor) -> ShardedGraph:
-        g = getattr(edge_index, "_sgf_sharded_graph", None)       # the relabelled list of a Repartition carries its graph
+        g = ops.hints_of(edge_index).sharded_graph                # the relabelled list of a Repartition carries its graph
         if g is not None:
             return g
         return ops.graph_cache.get(edge_index, -self.n_global - self.rank - 1,

@@ -3,7 +3,8 @@ large/ours.py:26-33), its locality-restoring node order and tile / row-block pla
 A^T backward (large/ours.py:34) on whichever kernel family the graph's structure selects.  `ops` re-exports every name."""
 from __future__ import annotations
 
-import ctypes
+import dataclasses
+import os
 from collections import OrderedDict
 from typing import Optional
 
@@ -13,14 +14,20 @@ from . import _lib
 from .kernels import HipKernels, LONG_ROW, _SEGMENT
 
 _F32 = torch.float32
-_BF16 = torch.bfloat16
 
 
 K = HipKernels()
 
-# Rows with more stored entries than this are reduced by whole workgroups, segment by segment
-# (sgf_spmm_split): one wave walking a 17 k-entry hub row of a power-law graph is a latency-bound tail.
-# LONG_ROW / _SEGMENT: the long-row threshold and segment length of the SpMM kernels (sgformer_amd/kernels.py)
+
+def _has(table, name: str, *args) -> bool:
+    """The kernel table has the method `name` — and, given arguments, answers them with yes (the *_supported queries).
+    hasattr is the rule on purpose: the CPU table of the tests lacks methods."""
+    fn = getattr(table, name, None)
+    return fn is not None and (not args or bool(fn(*args)))
+
+
+def _env(name: str, default: str = "") -> str:     # SGF_SPMM_* / SGF_REORDER as set NOW, never kept: tests flip them between calls
+    return os.environ.get(name, default)
 
 
 # Graphs with fewer stored entries than this are per-batch graphs (mini-batch trainers build one per step): their
@@ -46,10 +53,76 @@ def long_row_segments(rowptr: torch.Tensor, nnz: Optional[int] = None, max_row_l
     return int(segs.sum())
 
 
+@dataclasses.dataclass(slots=True)
+class EdgeHints:
+    """Promises of the producer of an `edge_index` (batching.subgraph, sampling.NeighborSampler, dist.Repartition), stored
+    under ONE attribute of the tensor: the reference trainers hand the tensor through code that stays unchanged."""
+    trusted: bool = False                    # ids are in range by construction: no range check (a host sync) in CSRGraph
+    max_in_degree: Optional[int] = None      # longest CSR row, as a bound the producer GUARANTEES (a sampler's largest fan-out)
+    csr: Optional[tuple] = None              # (rowptr, colind, val, deg) built with the edge list: sgf_csr_build's arrays, bit for bit
+    csr_t_lazy: bool = False                 # `csr` is directed, rows in ascending source order: sgf_sampled_csr_transpose serves A^T
+    symmetric: bool = False                  # A^T == A by construction (an induced subgraph of a parent verified once)
+    sharded_graph: object = None             # the dist.ShardedGraph of this (re-partitioned) list
+
+    def attach(self, edge_index: torch.Tensor) -> torch.Tensor:
+        edge_index._sgf_hints = self
+        return edge_index
+
+    def to(self, device) -> "EdgeHints":        # for a copy of the edge list on `device`: the CSR moves with it, a sharded graph does not
+        csr = None if self.csr is None else tuple(t.to(device) for t in self.csr)
+        return dataclasses.replace(self, csr=csr, sharded_graph=None)
+
+
+_NO_HINTS = EdgeHints()
+
+
+def hints_of(edge_index) -> EdgeHints:      # the record an edge list carries, or the shared all-default one (read only)
+    return getattr(edge_index, "_sgf_hints", _NO_HINTS)
+
+
 # ------------------------------------------------------------------------------------------------
 # T1: cached CSR of the normalised adjacency (large/ours.py:26-33)
 # ------------------------------------------------------------------------------------------------
-class CSRGraph:
+class GraphOperand:
+    """What spmm / spmm_on / _sharded_spmm read off a graph — the whole interface, with its defaults.  A subclass sets n, nnz,
+    device, rowptr / colind / val, long_segments / t_long_segments and `symmetric`, and implements transposed().  The flags are
+    plain attributes: GraphView.decide and dist.Repartition assign them from outside.  transposed() -> (rowptr, colind, val) of A^T."""
+    blocked = False          # multiply with the LDS-staged row-block plan (GraphView)
+    tiled = False            # ... with the matrix-core tile plan (GraphView)
+    locality = False         # the gathers mostly hit in L2 (a re-ordered graph): sgf_spmm_stream
+    comm_local = None        # int32 [n_local] community of every local row (dist.Repartition): row blocks of the own-block tile plan
+    blk_row = None           # int32 [nb + 1] row blocks that follow the communities (GraphView)
+    tile_min_count = None    # TilePlan's min_count when not the default (GraphView)
+    n_local = None           # rows of a node-sharded row block
+    symmetric: Optional[bool] = None
+    _t_lazy = False          # the edge list came with a sampled batch's CSR (sgf_sampled_csr_*)
+
+    def __init__(self):
+        self._plans, self._tile_plans, self._halo, self._view, self.forward_calls = {}, {}, {}, None, 0
+
+    def _stored(self, transposed: bool) -> bool:
+        """The orientation whose arrays serve A (False) or A^T (True): A^T of a symmetric graph is A."""
+        if transposed:
+            self.transposed()                  # (settles `symmetric` where it is not known yet)
+        return bool(transposed) and not self.symmetric
+
+    def arrays(self, transposed: bool = False):
+        """(rowptr, colind, val, long_segments) of A, or of A^T."""
+        if self._stored(transposed):
+            return (*self.transposed(), self.t_long_segments)
+        return self.rowptr, self.colind, self.val, self.long_segments
+
+    def plan(self, dtype, transposed: bool = False):      # BlockedPlan for `dtype` storage on A (or A^T), or None
+        return None
+
+    def halo(self, shard, transposed: bool):              # dist.HaloPlan of a node-sharded row block, or None: all-gather
+        return None
+
+    def view(self, now: bool = False) -> "GraphView":     # how the model should run on this graph: as it is
+        return GraphView(self, None, None)
+
+
+class CSRGraph(GraphOperand):
     """rowptr/colind/val of A = D^-1/2 (edge_index^T) D^-1/2 on the GPU, built by sgf_csr_build.
 
     The reference rebuilds this (degree + argsort over nnz) in every layer of every forward;
@@ -57,6 +130,7 @@ class CSRGraph:
     """
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int, validate: bool = True):
+        super().__init__()
         K.check(edge_index)
         if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
             raise ValueError("edge_index must be an int64 tensor of shape [2, nnz]")
@@ -64,36 +138,27 @@ class CSRGraph:
             raise ValueError("num_nodes must be < 2^31 (int32 column indices)")
         ei = edge_index.contiguous()
         n = int(num_nodes)
-        if getattr(edge_index, "_sgf_trusted", False):
-            validate = False      # produced by batching.subgraph / graph_prologue: ids are in range by construction
-        if validate and ei.shape[1] > 0:
+        hints = hints_of(edge_index)
+        if validate and not hints.trusted and ei.shape[1] > 0:
             lo, hi = torch.aminmax(ei)
             if int(lo) < 0 or int(hi) >= n:
                 raise IndexError(f"edge_index has node ids outside [0, {n})")
         self.n, self.nnz, self.device = n, int(ei.shape[1]), ei.device
         self.edge_index = ei
-        pre = getattr(edge_index, "_sgf_csr", None)
+        pre = hints.csr
         if pre is not None and pre[0].numel() == n + 1 and pre[1].numel() == self.nnz:
-            # the producer of this edge list (batching.subgraph on the parent's CSR: sgf_subgraph_csr_*) built the normalised
-            # CSR in the same pass — bit for bit what sgf_csr_build would return for it (tests/test_gpu_r05.py)
+            # built by the producer in its own pass (batching.subgraph: sgf_subgraph_csr_*, sampling.NeighborSampler:
+            # sgf_sampled_csr_build) — bit for bit what sgf_csr_build would return for this list (tests/test_gpu_r05.py)
             self.rowptr, self.colind, self.val, self.deg = pre
-            # a neighbour-sampled batch (sampling.NeighborSampler: sgf_sampled_csr_build): directed, its rows in ascending
-            # source order — transposed() takes sgf_sampled_csr_transpose
-            self._t_lazy = bool(getattr(edge_index, "_sgf_csr_t_lazy", False))
+            self._t_lazy = bool(hints.csr_t_lazy)
         else:
             self.rowptr, self.colind, self.val, self.deg = K.csr_build(ei, n)
-        # longest possible row: only a bound the caller GUARANTEES (sampling.NeighborSampler marks its batches with their
-        # largest fan-out).  The node count is no bound: sgf_csr_build keeps duplicate edges (large/ours.py:33 does not
-        # coalesce), so a row of a small multigraph can exceed LONG_ROW entries — without a hint the nnz-based
-        # bound (small graphs) or the exact count from rowptr applies.
-        hint = getattr(edge_index, "_sgf_max_in_degree", None)
-        self.long_segments = long_row_segments(self.rowptr, self.nnz, None if hint is None else int(hint))
+        # The node count is no bound on a row: sgf_csr_build keeps duplicate edges (large/ours.py:33 does not coalesce; ADVICE
+        # r04) — without the producer's the nnz-based bound (small graphs) or the exact count from rowptr applies.
+        self.long_segments = long_row_segments(self.rowptr, self.nnz, hints.max_in_degree)
         self.t_long_segments = 0
         self._t = None  # (rowptr, colind, val) of A^T, built on first backward
-        self.symmetric: Optional[bool] = None
-        if getattr(edge_index, "_sgf_symmetric", False):
-            # an induced subgraph of a graph whose A^T == A was verified once (batching.subgraph): symmetric by construction —
-            # no second sort, no comparison pass and no host read per batch in the first backward
+        if hints.symmetric:         # no second sort, no comparison pass and no host read per batch in the first backward
             self.symmetric, self._t, self.t_long_segments = True, (self.rowptr, self.colind, self.val), self.long_segments
 
     def transposed(self):
@@ -112,67 +177,42 @@ class CSRGraph:
             self.t_long_segments = self.long_segments if sym else long_row_segments(t_rowptr, self.nnz)
         return self._t
 
-    # ---- LDS-staged row-block SpMM: one plan per (orientation, storage dtype) ----
-    blocked = False          # set by GraphView when the plan serves enough entries from LDS
-    _t_lazy = False          # set when the edge list came with a sampled batch's CSR (sgf_sampled_csr_*)
-
     def plan(self, dtype, transposed: bool = False):
-        """BlockedPlan for SpMMs with `dtype` storage on this CSR (or its transpose), or None."""
+        """LDS-staged row-block SpMM: one BlockedPlan per (orientation, storage dtype) while `blocked` is set."""
         if not self.blocked:
             return None
-        if not hasattr(self, "_plans"):
-            self._plans = {}
-        if transposed:
-            self.transposed()
-            if self.symmetric:
-                transposed = False
-        key = (bool(transposed), dtype)
+        key = (self._stored(transposed), dtype)
         if key not in self._plans:
-            rp, ci, va = self.transposed() if transposed else (self.rowptr, self.colind, self.val)
-            self._plans[key] = BlockedPlan(rp, ci, va, self.n, dtype)
+            self._plans[key] = BlockedPlan(*self.arrays(key[0])[:3], self.n, dtype)
         return self._plans[key]
 
-    # ---- dense matrix-core tiles + gather remainder (sgf_spmm_tile): one plan per orientation ----
-    tiled = False            # set by GraphView when the tile plan covers enough of the stored entries
-    blk_row = None           # int32 [nb + 1] row blocks that follow the communities (GraphView)
-
     def tile_plan(self, transposed: bool = False):
-        if not hasattr(self, "_tile_plans"):
-            self._tile_plans = {}
-        if transposed:
-            self.transposed()
-            if self.symmetric:
-                transposed = False
-        if transposed not in self._tile_plans:
-            rp, ci, va = self.transposed() if transposed else (self.rowptr, self.colind, self.val)
-            self._tile_plans[transposed] = TilePlan(rp, ci, va, self.n, self.blk_row,
-                                                   min_count=getattr(self, "tile_min_count", None))
-        return self._tile_plans[transposed]
+        """Dense matrix-core tiles + gather remainder (sgf_spmm_tile): one TilePlan per orientation, on `blk_row`."""
+        key = self._stored(transposed)
+        if key not in self._tile_plans:
+            self._tile_plans[key] = TilePlan(*self.arrays(key)[:3], self.n, self.blk_row, min_count=self.tile_min_count)
+        return self._tile_plans[key]
 
     def view(self, now: bool = False) -> "GraphView":
         """How the model should run on this graph: the graph itself, or a re-ordered copy + the row
         permutation to apply at the module boundary (decided once; see GraphView).  now=True: decide
         at this call instead of waiting for the second forward."""
-        self.forward_calls = getattr(self, "forward_calls", 0) + 1
-        v = getattr(self, "_view", None)
-        if v is None:
-            v = GraphView.decide(self, now)
-            if v is not None:
-                self._view = v
-        return v if v is not None else GraphView(self, None, None)
+        self.forward_calls += 1
+        if self._view is None:
+            self._view = GraphView.decide(self, now)       # (None: undecided until the second forward)
+        return self._view if self._view is not None else GraphView(self, None, None)
 
 
-class WeightedCSRGraph:
+class WeightedCSRGraph(GraphOperand):
     """CSR of A[target, source] = value_e with EXPLICIT per-edge values — the edge-weighted variants of the
     medium recipes: GCNConv(x, edge_index, edge_weight) (medium/models.py:55-62, gcn_norm with weights) and
     DIFFormer's gcn_conv (medium/difformer.py:63-79, value = edge_weight * d_in * d_out).  The caller computes
     the values (one elementwise expression); entries are ordered by (target, source) like sgf_csr_build's, the
     transpose by (source, target).  No gradient flows to the values (edge weights are data, not parameters).
-    Same interface as CSRGraph towards ops.spmm."""
-
-    blocked = False
+    A GraphOperand without plans or views: the plain kernels."""
 
     def __init__(self, edge_index: torch.Tensor, values: torch.Tensor, num_nodes: int):
+        super().__init__()
         K.check(edge_index, values)
         n = int(num_nodes)
         self.n, self.nnz, self.device = n, int(edge_index.shape[1]), edge_index.device
@@ -195,9 +235,6 @@ class WeightedCSRGraph:
             self.t_long_segments = long_row_segments(self._t[0], self.nnz)
         return self._t
 
-    def plan(self, dtype, transposed=False):
-        return None
-
 
 def weighted_graph(edge_index: torch.Tensor, edge_weight: torch.Tensor, num_nodes: int, value_fn, tag: str):
     """Cached WeightedCSRGraph; `value_fn(edge_index, edge_weight, n)` -> (edge_index', values) builds the
@@ -215,9 +252,8 @@ def weighted_graph(edge_index: torch.Tensor, edge_weight: torch.Tensor, num_node
 
 # SGF_SPMM_BLOCK = "rows_per_block,lds_rows" overrides the block shape (default: 128 rows, all 144 KiB of LDS)
 def _block_shape(dtype):
-    import os
     cap = K.lds_rows_max(dtype)
-    env = os.environ.get("SGF_SPMM_BLOCK", "")
+    env = _env("SGF_SPMM_BLOCK")
     if env:
         r, c = (int(t) for t in env.split(","))
         return r, min(c, cap)
@@ -249,8 +285,7 @@ TILE_SPARSE_DENSITY = 0.12
 
 
 def _tile_params():
-    import os
-    env = os.environ.get("SGF_SPMM_TILE", "")          # "cap,min_count,max_rows" (experiments)
+    env = _env("SGF_SPMM_TILE")          # "cap,min_count,max_rows" (experiments)
     if env:
         c, m, r = (int(t) for t in env.split(","))
         return c, m, r
@@ -302,10 +337,7 @@ def set_reorder_mode(mode: Optional[str]):
 
 
 def _mode() -> str:
-    if _reorder_mode is not None:
-        return _reorder_mode
-    import os
-    return {"0": "never", "1": "always"}.get(os.environ.get("SGF_REORDER", "auto"), "auto")
+    return _reorder_mode or {"0": "never", "1": "always"}.get(_env("SGF_REORDER", "auto"), "auto")
 
 
 class GraphView:
@@ -326,20 +358,18 @@ class GraphView:
                 return GraphView(g, None, None, {"reordered": False, "why": "small graph"})
             if not now and g.forward_calls < 2:
                 return None                    # undecided: wait for the second forward on this graph
-        import os
         perm, inv, comm = K.reorder(g.edge_index, g.n, *REORDER_ITERS)
         g2 = CSRGraph(inv.long()[g.edge_index], g.n, validate=False)
         # how much neighbour sharing the new order exposes: the share of stored entries that fall into the dense
         # tiles of community-aligned row blocks — the adoption criterion, whichever kernel then runs
-        _, _, max_rows = _tile_params()
-        g2.blk_row = K.tile_blocks(comm[perm.long()].contiguous(), g.n, max_rows, g.device)
+        g2.blk_row = K.tile_blocks(comm[perm.long()].contiguous(), g.n, _tile_params()[2], g.device)
         try:
             tp = g2.tile_plan(False)
         except (ValueError, _lib.SgfError) as e:
             # a plan the tile kernel cannot take (a row block out of range, nnz beyond its 32-bit offsets): keep the graph
             # as given rather than fail the forward
             return GraphView(g, None, None, {"reordered": False, "why": f"tile plan unsupported: {e}"})
-        if tp.tile_density < TILE_SPARSE_DENSITY and tp.min_count == TILE_MIN_COUNT and not os.environ.get("SGF_SPMM_TILE"):
+        if tp.tile_density < TILE_SPARSE_DENSITY and tp.min_count == TILE_MIN_COUNT and not _env("SGF_SPMM_TILE"):
             # tiles this sparse (a skewed graph: many sources referenced just twice per block) move more fragment bytes
             # than the gathers they replace: stage only sources with one more reference (power-law community graph at
             # ogbn-products scale: density 0.08 -> 0.11, 3.08 -> 2.92 ms; profiles/r03_spmm_tile.md)
@@ -354,8 +384,8 @@ class GraphView:
         # for bf16 rows of 128 / 256 features; the flattened stream kernel (sgf_spmm_stream) otherwise and under
         # SGF_SPMM_TILED=0; SGF_SPMM_BLOCKED=1 selects r02's LDS-staged row blocks (profiles/r02_spmm_structured.md).
         g2.locality = True        # its gathers mostly hit in L2: ops.spmm_on picks sgf_spmm_stream
-        g2.blocked = os.environ.get("SGF_SPMM_BLOCKED", "0") == "1"
-        g2.tiled = os.environ.get("SGF_SPMM_TILED", "1") == "1" and not g2.blocked
+        g2.blocked = _env("SGF_SPMM_BLOCKED", "0") == "1"
+        g2.tiled = _env("SGF_SPMM_TILED", "1") == "1" and not g2.blocked
         if not g2.tiled:
             g2._tile_plans.clear()
         stats["kernel"] = ("row-block (LDS-staged)" if g2.blocked else
@@ -413,15 +443,14 @@ def _sharded_spmm(graph, x, shard, transposed: bool):
     the product — the operand is split into column chunks, every chunk's all-gather is issued up front
     (asynchronously, on the collective's own stream), and the SpMM of chunk c starts as soon as chunk c has
     arrived while chunks c+1.. are still on the xGMI links."""
-    rowptr, colind, val = graph.transposed() if transposed else (graph.rowptr, graph.colind, graph.val)
-    long_segments = graph.t_long_segments if transposed else graph.long_segments
+    rowptr, colind, val, long_segments = graph.arrays(transposed)
     n_local = graph.n_local
-    plan = graph.halo(shard, transposed) if hasattr(graph, "halo") else None
+    plan = graph.halo(shard, transposed)
     if plan is not None and plan.enabled:
         if plan.n_halo == 0:                      # nothing to exchange (one rank, or a block without cut edges)
             return _own_block_spmm(graph, plan, (rowptr, plan.colind, val, long_segments), x, n_local, transposed)
-        if getattr(shard, "overlap", False):
-            shard.overlapped_exchanges = getattr(shard, "overlapped_exchanges", 0) + 1
+        if shard.overlap:
+            shard.overlapped_exchanges += 1
             # the entries whose source this rank owns are multiplied while the halo rows are on the links; the halo
             # entries follow when they have arrived (their sum is rounded to the storage dtype before it is added: bf16
             # rows with cut edges carry two roundings more than the single-GPU product)
@@ -446,34 +475,34 @@ def _sharded_spmm(graph, x, shard, transposed: bool):
     return y
 
 
+def _tile_operand_ok(x: torch.Tensor, out=None) -> bool:
+    """sgf_spmm_tile takes x (and `out`): a width and dtype it has kernels for, an operand within its 32-bit byte offsets (= the
+    entry's own bound), rows of `out` it can store 16 bytes at a time."""
+    return (_has(K, "tile_supported", x.shape[1], x.dtype)
+            and x.shape[0] * max(x.stride(0), x.shape[1]) * 2 < 2 ** 32 - 2048
+            and (out is None or (out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0)))
+
+
 def _own_block_spmm(graph, plan, own, x, n_local: int, transposed: bool):
     """The square block of a rank's rows x the rank's OWN columns (the part of a node-sharded product that needs no
     exchange).  When the partition follows sgf_reorder's order (dist.Repartition sets graph.locality / comm_local) this
-    block has the structure the re-ordered single-GPU graph has, and takes the same kernels: the matrix-core tile kernel
-    (sgf_spmm_tile, bf16 rows of 128 / 256 features; plan built once per block and direction) or the stream kernel; the
-    plain row kernel otherwise."""
+    block has the structure the re-ordered single-GPU graph has, and takes the same kernels: the matrix-core tile kernel (bf16
+    rows of 128 / 256 features; one plan per HaloPlan: None = undecided, False = no) or the stream kernel; else the row kernel."""
     rp, ci, va, segs = own
-    if getattr(graph, "locality", False):
-        import os
-        if (hasattr(K, "tile_supported") and K.tile_supported(x.shape[1], x.dtype) and getattr(graph, "comm_local", None) is not None
-                and os.environ.get("SGF_SPMM_TILED", "1") == "1" and n_local >= 256
-                and x.shape[0] * max(x.stride(0), x.shape[1]) * 2 < 2 ** 32 - 2048):
-            plans = plan.__dict__.setdefault("_own_tile_plans", {})
-            tp = plans.get("plan")
-            if tp is None:
-                try:
-                    _, _, max_rows = _tile_params()
-                    blk_row = K.tile_blocks(graph.comm_local, n_local, max_rows, x.device)
-                    tp = TilePlan(rp, ci, va, n_local, blk_row)
-                    if tp.tile_fraction < REORDER_MIN_LDS_FRACTION:
-                        tp = False                              # too little to put on the matrix cores: stream kernel
-                except (ValueError, _lib.SgfError):
-                    tp = False
-                plans["plan"] = tp
-            if tp:
-                return K.spmm_tile(tp, x, n_local)
-        return K.spmm(rp, ci, va, x, n_local, long_segments=segs, stream_hint=True)
-    return K.spmm(rp, ci, va, x, n_local, long_segments=segs)
+    if not graph.locality:
+        return K.spmm(rp, ci, va, x, n_local, long_segments=segs)
+    if (_tile_operand_ok(x) and graph.comm_local is not None and _env("SGF_SPMM_TILED", "1") == "1" and n_local >= 256):
+        if plan.own_tile_plan is None:
+            try:
+                blk_row = K.tile_blocks(graph.comm_local, n_local, _tile_params()[2], x.device)
+                tp = TilePlan(rp, ci, va, n_local, blk_row)
+                # too little to put on the matrix cores: stream kernel
+                plan.own_tile_plan = tp if tp.tile_fraction >= REORDER_MIN_LDS_FRACTION else False
+            except (ValueError, _lib.SgfError):
+                plan.own_tile_plan = False
+        if plan.own_tile_plan:
+            return K.spmm_tile(plan.own_tile_plan, x, n_local)
+    return K.spmm(rp, ci, va, x, n_local, long_segments=segs, stream_hint=True)
 
 
 class _SpMM(torch.autograd.Function):
@@ -495,39 +524,32 @@ class _SpMM(torch.autograd.Function):
         return spmm_on(graph, gy.contiguous(), True), None, None, None
 
 
-def _row_kernel_graph(graph) -> bool:
-    """spmm_on's last branch: no row-block plan, no tile plan, no locality hint — the launch that may run k_spmm_row."""
-    return not (getattr(graph, "blocked", False) or getattr(graph, "tiled", False) or getattr(graph, "locality", False))
-
-
 def spmm_packed_slot(graph, x_shape, dtype, slot_bytes: int) -> int:
     """`slot_bytes` if A x for a contiguous x of this shape would gather a packed copy of x with slots of that size
     (K.bn_apply_packed -> spmm(..., packed=...)), else 0: the graph takes the wave-per-row launch and the launcher's own
     rule holds (bf16 rows of 256 columns, SGF_SPMM_PACKED).  Rows on the long-row path are reduced from the dense x."""
-    if not slot_bytes or not hasattr(K, "spmm_packed_supported") or not _row_kernel_graph(graph):
-        return 0
+    if not slot_bytes or not _has(K, "spmm_packed_supported") or graph.blocked or graph.tiled or graph.locality:
+        return 0                   # (spmm_on's last two branches only: no row-block plan, no tile plan, no locality hint)
     return slot_bytes if K.spmm_packed_supported(x_shape, dtype, slot_bytes) else 0
 
 
 def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None) -> torch.Tensor:
-    """A x or A^T x on one GPU: the LDS-staged row-block kernel when the graph carries a plan for this
-    storage dtype (GraphView adopted a re-ordered CSR), else the wave-per-row kernel.  `packed`: the producer's packed
-    copy of x (K.bn_apply_packed), gathered instead of x by the wave-per-row launch of A x."""
-    rp, ci, va = graph.transposed() if transposed else (graph.rowptr, graph.colind, graph.val)
-    segs = graph.t_long_segments if transposed else graph.long_segments
-    plan = graph.plan(x.dtype, transposed) if (getattr(graph, "blocked", False) and x.shape[1] <= 256) else None
+    """A x or A^T x on one GPU, on the first kernel that applies: the LDS-staged row-block kernel (graph.blocked, rows of at most
+    256 columns); matrix-core tiles + gather remainder (graph.tiled and _tile_operand_ok); the stream kernel (graph.locality);
+    the wave-per-row launch gathering `packed`, the producer's packed copy of x (K.bn_apply_packed; A x into a fresh tensor
+    only); else the wave-per-row kernel on x, long rows split over workgroups."""
+    rp, ci, va, segs = graph.arrays(transposed)
+    plan = graph.plan(x.dtype, transposed) if (graph.blocked and x.shape[1] <= 256) else None
     if plan is not None:
         return K.spmm_blocked(rp, plan, x, graph.n, out=out, long_segments=segs)
-    if getattr(graph, "tiled", False):
-        if (K.tile_supported(x.shape[1], x.dtype)
-                and x.shape[0] * max(x.stride(0), x.shape[1]) * 2 < 2 ** 32 - 2048      # = sgf_spmm_tile's own bound
-                and (out is None or (out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0))):
+    if graph.tiled:
+        if _tile_operand_ok(x, out):
             return K.spmm_tile(graph.tile_plan(transposed), x, graph.n, out=out)
-        if not K.tile_supported(x.shape[1], x.dtype) and getattr(graph, "_tile_plans", None):
+        if not K.tile_supported(x.shape[1], x.dtype) and graph._tile_plans:
             # this graph is being multiplied in a storage dtype / width the tile kernel does not take (fp32 runs): the plan
             # GraphView.decide built for its adoption statistics (about the size of the CSR) is dropped, not kept resident
             graph._tile_plans.clear()
-    if getattr(graph, "locality", False):
+    if graph.locality:
         return K.spmm(rp, ci, va, x, graph.n, out=out, long_segments=segs, stream_hint=True)
     if packed is not None and not transposed and out is None:
         return K.spmm_packed(rp, ci, va, x, packed, graph.n, long_segments=segs)
@@ -537,6 +559,4 @@ def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None) -> 
 def spmm(graph, x: torch.Tensor, shard=None, packed=None) -> torch.Tensor:
     """Y = A X with A the cached normalised adjacency (torch_sparse.matmul(adj, x) in the reference).  `packed`: a packed
     copy of X for the forward gathers (spmm_packed_slot says when one is of use); the backward never reads it."""
-    if packed is None:
-        return _SpMM.apply(x, graph, shard)
     return _SpMM.apply(x, graph, shard, packed)

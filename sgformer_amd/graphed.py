@@ -145,6 +145,7 @@ class StaticCSR(ops.CSRGraph):
     SpMM launches hold THESE addresses; `load` puts a batch's arrays there.  A^T == A (the caller checked)."""
 
     def __init__(self, n: int, cap: int, device, long_segments: int):          # (not CSRGraph.__init__: nothing is built)
+        ops.GraphOperand.__init__(self)
         self.n, self.nnz, self.cap, self.device = n, 0, cap, device
         self.edge_index = None
         self.rowptr = torch.zeros(n + 1, dtype=torch.int64, device=device)
@@ -161,8 +162,7 @@ class StaticCSR(ops.CSRGraph):
         self.colind[:nnz].copy_(colind)
         self.val[:nnz].copy_(val)
 
-    def view(self, now: bool = False):
-        return ops.GraphView(self, None, None)
+    view = ops.GraphOperand.view              # as it is: a batch graph is never re-ordered
 
 
 class _Core(nn.Module):
@@ -224,9 +224,10 @@ class _Entry:
 def _eligible(model, x, edge_index) -> bool:
     if not (enabled() and model.training and torch.is_grad_enabled() and x.is_cuda and not x.requires_grad):
         return False
-    if not getattr(edge_index, "_sgf_symmetric", False) or x.shape[0] < _MIN_NODES:
+    hints = ops.hints_of(edge_index)
+    if not hints.symmetric or x.shape[0] < _MIN_NODES:
         return False
-    csr = edge_index._sgf_csr
+    csr = hints.csr
     if csr[0].numel() != x.shape[0] + 1 or csr[1].numel() != edge_index.shape[1]:
         return False          # (not the CSR of THIS call's graph: the eager path builds its own, as ops.CSRGraph decides too)
     if not model.use_graph or model.graph_conv._shard is not None:
@@ -247,7 +248,7 @@ def _long_bound(edge_index, cap: int) -> int:
     """`long_segments` of the captured SpMM launches.  The long-row path is an optimisation (the row kernel is correct for any
     row length): a capture without it stays right for a later batch that does have a long row, a capture with it sizes its
     queue for the worst case at capacity (the bound of ops.long_row_segments)."""
-    hint = getattr(edge_index, "_sgf_max_in_degree", None)
+    hint = ops.hints_of(edge_index).max_in_degree
     if hint is not None and int(hint) <= ops.LONG_ROW:
         return 0
     return cap // ops._SEGMENT + cap // (ops.LONG_ROW + 1) + 1
@@ -258,7 +259,7 @@ def _capture(model, entry: _Entry, x, edge_index, cdt, out_dtype):
     nnz = int(edge_index.shape[1])
     cap = max(1024, int(nnz * 1.25) + 4096)
     graph = StaticCSR(n, cap, dev, _long_bound(edge_index, cap))
-    graph.load(*edge_index._sgf_csr[:3])
+    graph.load(*ops.hints_of(edge_index).csr[:3])
     core = _Core(model, graph, cdt, out_dtype)
     core.train(model.training)
     names, params = zip(*core.named_parameters())
@@ -330,7 +331,7 @@ def maybe_step(model, x, edge_index, cdt, out_dtype):
     # (large/main-batch.py:142); anything else keeps the eager path.
     if any(p.grad is not None for p in model.parameters()):
         return None
-    csr = edge_index._sgf_csr
+    csr = ops.hints_of(edge_index).csr
     nnz = int(csr[1].numel())
     # captured launches hold the parameters' addresses, which of them get a gradient and the dropout probabilities: moved
     # (the trainer's evaluation round trip), replaced or (un)frozen parameters and a changed `dropout` mean a new capture

@@ -15,19 +15,12 @@ from .kernels import _pair_gram, _rows, _rows16
 _F32 = torch.float32
 _BF16 = torch.bfloat16
 
-from .graph import K  # noqa: E402,F401  (ONE kernel table, rebound in every module by ops.set_kernels)
+from .graph import K, _has  # noqa: E402,F401  (ONE kernel table, rebound in every module by ops.set_kernels; one probe)
 
 
 def _f32c(t):
     """A parameter (or None) as the kernels read it: fp32, contiguous, outside autograd."""
     return None if t is None else t.detach().float().contiguous()
-
-
-def _has(table, name: str, *args) -> bool:
-    """The kernel table has the method `name` — and, given arguments, answers them with yes (the *_supported queries).
-    hasattr is the rule on purpose: the CPU table of the tests lacks methods."""
-    fn = getattr(table, name, None)
-    return fn is not None and (not args or bool(fn(*args)))
 
 
 def _switch(name: str, default: bool) -> bool:

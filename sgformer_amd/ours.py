@@ -625,7 +625,7 @@ class SGFormer(nn.Module):
         ops._require_cuda(x, edge_index)
         out_dtype = x.dtype if getattr(self, 'logits_dtype', None) is None else self.logits_dtype
         cdt = self.compute_dtype if self.compute_dtype is not None else x.dtype
-        if getattr(edge_index, "_sgf_csr", None) is not None:
+        if ops.hints_of(edge_index).csr is not None:
             # a mini-batch whose CSR came with its edge list (batching.subgraph): batches of one node count replay ONE captured
             # hipGraph per direction instead of ~150 launches (sgformer_amd/graphed.py; SGF_BATCH_GRAPH=0 turns it off)
             from . import graphed

@@ -39,10 +39,7 @@ class SampledBatch:
         out = SampledBatch(mv(self.x), mv(self.edge_index), mv(self.y), self.batch_size, mv(self.n_id))
         if out.edge_index is not self.edge_index:
             # what ops.CSRGraph reads off a sampled edge list (the batch's CSR moves with it)
-            for attr in ("_sgf_trusted", "_sgf_max_in_degree", "_sgf_csr", "_sgf_csr_t_lazy"):
-                if hasattr(self.edge_index, attr):
-                    v = getattr(self.edge_index, attr)
-                    setattr(out.edge_index, attr, tuple(mv(t) for t in v) if attr == "_sgf_csr" else v)
+            ops.hints_of(self.edge_index).to(dev).attach(out.edge_index)
         return out
 
 
@@ -143,8 +140,8 @@ class NeighborSampler:
         n_id32 = torch.cat(nodes)
         _launch(dev, "sgf_neighbor_sample_mark", self.local_of, n_id32, int(n_id32.numel()), -1)
         ei = torch.stack([torch.cat(srcs), torch.cat(dsts)]).long() if srcs else torch.zeros(2, 0, dtype=torch.int64, device=dev)
-        ei._sgf_trusted = True          # local ids are in range by construction: ops.CSRGraph skips its host check
-        return n_id32.long(), ei, bs
+        # local ids are in range by construction: ops.CSRGraph skips its host check
+        return n_id32.long(), ops.EdgeHints(trusted=True).attach(ei), bs
 
     def _batch_capacity(self, bs: int) -> int:
         """Worst-case number of sampled entries of one batch: bs * (k1 + k1 k2 + ...)."""
@@ -181,13 +178,13 @@ class NeighborSampler:
         nn, ne = (int(v) for v in counts[:2].tolist())          # the one host read of the batch
         self.host_reads += 1
         ei = torch.stack([e_src[:ne], e_dst[:ne]]).long()
-        ei._sgf_trusted = True
-        ei._sgf_max_in_degree = max(self.fanouts)       # every node is a frontier node once: at most fan-out in-edges
         if csr is not None:
             rowptr_b, colind_b, val_b, deg_b = csr
-            ei._sgf_csr = (rowptr_b[:nn + 1], colind_b[:ne], val_b[:ne], deg_b[:nn])     # ops.CSRGraph adopts these
-            ei._sgf_csr_t_lazy = True       # ... and transposes them with sgf_sampled_csr_transpose (no symmetry test, no host read)
-        return nodes[:nn].long(), ei, bs
+            csr = (rowptr_b[:nn + 1], colind_b[:ne], val_b[:ne], deg_b[:nn])
+        # every node is a frontier node once: at most fan-out in-edges; ops.CSRGraph adopts the CSR and transposes it with
+        # sgf_sampled_csr_transpose (no symmetry test, no host read)
+        hints = ops.EdgeHints(trusted=True, max_in_degree=max(self.fanouts), csr=csr, csr_t_lazy=csr is not None)
+        return nodes[:nn].long(), hints.attach(ei), bs
 
     def _hops(self, nodes, srcs, dsts, frontier, local0, n_known, batch_id):
         """The hop-by-hop path (a fan-out of -1 has no a-priori capacity): one sgf_neighbor_sample_hop per hop, its edge and

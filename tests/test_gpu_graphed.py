@@ -296,7 +296,7 @@ def test_a_batch_beyond_the_captured_capacity_and_a_first_long_row(cuda, monkeyp
             out = model(x[idx.to(cuda)], ei_i)
             out.float().sum().backward()
             outs.append(out.detach().float().clone())
-            info.append((int(ei_i.shape[1]), int(getattr(ei_i, "_sgf_max_in_degree", 0))))
+            info.append((int(ei_i.shape[1]), int(ops.hints_of(ei_i).max_in_degree or 0)))
         used = {k: graphed.counters[k] - before[k] for k in before}
         ops.graph_cache.clear()
         return outs, used, info

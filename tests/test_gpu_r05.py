@@ -111,7 +111,7 @@ def test_subgraph_from_the_parent_csr_is_bit_exact(cuda, kind):
     eid, subd = ei.to(cuda), subset.to(cuda)
     batching._parents.clear()
     out, _ = batching.subgraph(subd, eid, num_nodes=n, relabel_nodes=True)
-    assert hasattr(out, "_sgf_csr") and out._sgf_trusted
+    assert ops.hints_of(out).csr is not None and ops.hints_of(out).trusted
     m = subset.numel()
     # the reference semantics on the host: mask + relabel, original order
     pos = torch.full((n,), -1, dtype=torch.long)
@@ -122,18 +122,18 @@ def test_subgraph_from_the_parent_csr_is_bit_exact(cuda, kind):
     key = lambda e: torch.sort(e[1] * m + e[0])[0]       # noqa: E731
     assert torch.equal(key(out.cpu()), key(ref_ei))
     rowptr, colind, val, deg = O.csr_build(ref_ei.numpy(), m)
-    rb, cb, vb, db = (t.cpu().numpy() for t in out._sgf_csr)
+    rb, cb, vb, db = (t.cpu().numpy() for t in ops.hints_of(out).csr)
     assert np.array_equal(rb, rowptr) and np.array_equal(cb, colind.astype(np.int32)) and np.array_equal(db, deg.astype(np.int32))
     assert np.array_equal(vb.view(np.uint32), val.view(np.uint32))
-    assert out._sgf_max_in_degree == (int(np.diff(rowptr).max()) if m else 0)     # total[2] of sgf_subgraph_csr_plan
+    assert ops.hints_of(out).max_in_degree == (int(np.diff(rowptr).max()) if m else 0)     # total[2] of sgf_subgraph_csr_plan
     # the emitted edge list is in (target, source) order: exactly the CSR's
     assert np.array_equal(out[1].cpu().numpy(), np.repeat(np.arange(m), np.diff(rowptr))) and np.array_equal(out[0].cpu().numpy(), colind)
     parent = next(iter(batching._parents.values()))[1]
     assert int((parent.local_of != -1).sum()) == 0
-    assert parent.symmetric == (kind == "undirected") and bool(getattr(out, "_sgf_symmetric", False)) == (kind == "undirected")
+    assert parent.symmetric == (kind == "undirected") and bool(ops.hints_of(out).symmetric) == (kind == "undirected")
     # ops.CSRGraph adopts the arrays (no second sort) and the SpMM on them equals the SpMM on a freshly built CSR
     gr = ops.CSRGraph(out, m)
-    assert gr.rowptr.data_ptr() == out._sgf_csr[0].data_ptr()
+    assert gr.rowptr.data_ptr() == ops.hints_of(out).csr[0].data_ptr()
     fresh = ops.CSRGraph(ref_ei.to(cuda), m)
     x = torch.randn(m, 64, generator=g).to(cuda)
     assert torch.equal(ops.spmm_on(gr, x, False), ops.spmm_on(fresh, x, False))
@@ -142,4 +142,4 @@ def test_subgraph_from_the_parent_csr_is_bit_exact(cuda, kind):
     # a subset that repeats a node takes the general path (and leaves the table clean)
     dup = torch.cat([subd[:10], subd[:3]])
     out2, _ = batching.subgraph(dup, eid, num_nodes=n, relabel_nodes=True)
-    assert not hasattr(out2, "_sgf_csr") and int((parent.local_of != -1).sum()) == 0
+    assert ops.hints_of(out2).csr is None and int((parent.local_of != -1).sum()) == 0

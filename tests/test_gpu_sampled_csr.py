@@ -34,13 +34,13 @@ def _check_batch(e, nn, carried: bool):
     want = HipKernels.csr_build(e, nn)
     assert want[0].dtype == torch.int64 and want[1].dtype == torch.int32 and want[3].dtype == torch.int32
     if carried:
-        assert e._sgf_csr_t_lazy is True
-        _same(e._sgf_csr, want, "carried CSR")
+        assert ops.hints_of(e).csr_t_lazy is True
+        _same(ops.hints_of(e).csr, want, "carried CSR")
     else:
-        assert not hasattr(e, "_sgf_csr") and not hasattr(e, "_sgf_csr_t_lazy")
+        assert ops.hints_of(e).csr is None and not ops.hints_of(e).csr_t_lazy
     g = ops.CSRGraph(e, nn)
     if carried:
-        assert g.rowptr.data_ptr() == e._sgf_csr[0].data_ptr()            # adopted, not rebuilt
+        assert g.rowptr.data_ptr() == ops.hints_of(e).csr[0].data_ptr()   # adopted, not rebuilt
     _same((g.rowptr, g.colind, g.val, g.deg), want, "CSRGraph")
     t_want = HipKernels.csr_transpose(e, nn, want[3], want[0], want[1])
     t = g.transposed()
@@ -191,7 +191,7 @@ def test_training_step_needs_neither_old_entry_and_reads_the_host_once(cuda, mon
     reads, batches = loader.sampler.host_reads, 0
     for graph in loader:
         graph = graph.to(cuda)
-        assert hasattr(graph.edge_index, "_sgf_csr") and graph.edge_index._sgf_csr_t_lazy
+        assert ops.hints_of(graph.edge_index).csr is not None and ops.hints_of(graph.edge_index).csr_t_lazy
         before = loader.sampler.host_reads
         loss = _step(m, graph)
         assert loader.sampler.host_reads == before
@@ -206,9 +206,9 @@ def test_training_step_needs_neither_old_entry_and_reads_the_host_once(cuda, mon
     assert calls["t"] == batches
     # the attributes travel with the batch (SampledBatch.to), the CSR to the same device as its edge list
     moved = graph.to("cpu")
-    assert moved.edge_index._sgf_csr_t_lazy and moved.edge_index._sgf_trusted
-    assert all(t.device.type == "cpu" for t in moved.edge_index._sgf_csr)
-    assert all(torch.equal(a, b.cpu()) for a, b in zip(moved.edge_index._sgf_csr, graph.edge_index._sgf_csr))
+    assert ops.hints_of(moved.edge_index).csr_t_lazy and ops.hints_of(moved.edge_index).trusted
+    assert all(t.device.type == "cpu" for t in ops.hints_of(moved.edge_index).csr)
+    assert all(torch.equal(a, b.cpu()) for a, b in zip(ops.hints_of(moved.edge_index).csr, ops.hints_of(graph.edge_index).csr))
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
@@ -224,7 +224,7 @@ def test_same_arithmetic_with_the_switch_on_and_off(cuda, monkeypatch, dtype):
         loader, f, c = _task(cuda, feature_dtype=dt)
         m = _model(cuda, f, c, compute_dtype=dt)
         graph = next(iter(loader))
-        assert hasattr(graph.edge_index, "_sgf_csr") == (flag == "1")
+        assert (ops.hints_of(graph.edge_index).csr is not None) == (flag == "1")
         loss = _step(m, graph)
         res[flag] = (graph.n_id.clone(), graph.edge_index.clone(), loss.clone(),
                      {k: p.grad.detach().clone() for k, p in m.named_parameters()})

@@ -42,7 +42,7 @@ def test_wrappers_return_what_the_plain_lines_return(cuda, monkeypatch):
 def test_the_host_does_not_wait_for_the_compute_stream(cuda, monkeypatch):
     """~100 ms of matrix products queued on the current stream, then the trainer's gather lines: with the prep stream the host
     is through them long before the compute stream has drained, and what the compute stream then reads is right."""
-    from sgformer_amd import batching, staging, synth
+    from sgformer_amd import batching, ops, staging, synth
     monkeypatch.setenv("SGF_PREP_STREAM", "1")
     g = torch.Generator().manual_seed(1)
     n = 200000
@@ -79,7 +79,7 @@ def test_the_host_does_not_wait_for_the_compute_stream(cuda, monkeypatch):
     assert torch.equal(out, ref)
     monkeypatch.setenv("SGF_PREP_STREAM", "0")
     ei_ref, _ = batching.subgraph(idx, ei, num_nodes=n, relabel_nodes=True)
-    assert torch.equal(ei_i, ei_ref) and all(torch.equal(p, q) for p, q in zip(ei_i._sgf_csr, ei_ref._sgf_csr))
+    assert torch.equal(ei_i, ei_ref) and all(torch.equal(p, q) for p, q in zip(ops.hints_of(ei_i).csr, ops.hints_of(ei_ref).csr))
     batching._parents.clear()
 
 
