@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 664 /* 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 665 /* 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -1067,6 +1067,60 @@ size_t sgf_argmax_workspace_bytes(int64_t m, int32_t c);
 int sgf_argmax_count(const void* logits, int64_t ldl, int64_t n, int32_t c, int32_t dtype, const void* labels,
                      int64_t label_stride, int32_t label_kind, const int64_t* idx, int64_t m, int64_t* counts,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N6 — the head, its loss and their gradient on the SEED rows of a neighbour-sampled batch.   Replaces 100M/nb-sample.py:29
+ * and :41 around 100M/ours.py's last two lines
+ *     output = model(graph.x, graph.edge_index)[:batch_size];  loss = nn.CrossEntropyLoss()(output, graph.y[:batch_size])
+ * which compute, store and differentiate all n rows of the logits to read m of them (1 000 of 756 000 for fan-outs
+ * [15, 10, 5]).  Selected rows r_j, j < m: the PREFIX 0..m-1 when idx == NULL, else idx int64 [m], distinct, in [0, n)
+ * (the convention of sgf_nll_* / sgf_bce_*; an entry outside [0, n) is clamped into it, never used as it is).
+ *
+ * sgf_head_rows_fwd :  z_j = round_to_storage(a x1[r_j] + b x2[r_j])      (x2 == NULL: z_j = round(a x1[r_j]))
+ *                      logits[j] = z_j W^T + bias                          fp32 [m, classes] COMPACT, leading dim ldl
+ *   x1 / x2 [n, d] in the storage dtype (leading dims ld1 / ld2, rows 16-byte aligned), w fp32 [classes, d] row-major,
+ *   bias fp32 [classes].  z is rounded where the unfused sgf_axpby rounds it.  SGF_BF16: z and W (rounded to bf16 as
+ *   sgf_combine_fc_fwd rounds it) on the bf16 matrix cores, fp32 accumulation.  SGF_F32: the fp32 operands as they are,
+ *   whatever the matmul-precision setting, accumulated in fp64 and rounded to fp32 once (SGF_F32_BF16X3 is not accepted).  Shapes (sgf_head_rows_supported): d <= 256 with
+ *   d % 32 == 0 (bf16) or d % 4 == 0 (fp32), any 1 <= classes <= 256 — ragged class counts are masked in the kernel, no
+ *   padded copy of W or bias is made.
+ *   labels != NULL (int64 [m], one per SELECTED row, compact): the same launch also leaves
+ *       lse      fp32 [m]    log-sum-exp of every selected row
+ *       loss_sum fp32 [1]    - sum_j (logits[j][labels[j]] - lse[j]) over the rows whose label is in [0, classes)
+ *       counts   int64 [2]   { rows with a label in [0, classes); of those, rows whose first maximal column is the label }
+ *   (argmax as sgf_argmax_count: first maximal column, a NaN is the maximum).  A label outside [0, classes) adds nothing,
+ *   is not counted and gets a zero gradient row (nn.CrossEntropyLoss's ignore_index).  Deterministic: per-block partials
+ *   in `workspace` (sgf_head_rows_fwd_workspace_bytes(m); not needed without labels), summed in a fixed order.
+ *   m == 0: loss_sum = 0, counts = {0, 0}, no launch.
+ *
+ * sgf_head_rows_bwd :  the gradient g [m, classes] is the caller's (dlogits fp32 [m, classes], leading dim lddl; any
+ *   loss on the m rows) or, with dlogits == NULL, formed in registers from the forward's logits / lse and the labels:
+ *       g_j = gout[0] * inv_denom * (softmax(logits[j]) - onehot(labels[j]))       (gout fp32 [1] on the device)
+ *   (the label's own entry as minus the sum of the row's other entries: no cancellation where its probability is near 1)
+ *   Results:
+ *       dx1[r_j] = a (g_j W), dx2[r_j] = b (g_j W), rounded once to the storage dtype; EVERY other row of dx1 / dx2
+ *                  ([n, d], leading dims ldd1 / ldd2, rows 16-byte aligned) is written as exact zeros by the same call
+ *                  (prefix form: one launch that also streams the zeros; idx form: a zero fill, then the row scatter).
+ *                  dx2 == NULL exactly when x2 == NULL.
+ *       dw fp32 [classes, d] = g^T z,  db fp32 [classes] = sum_j g_j — reduced over the m rows in fixed row slices added
+ *                  in a fixed order; z is recomputed from the m rows of x1 / x2, nothing of size n is read.  g enters
+ *                  this reduction in fp32; dX's product takes it as the forward takes z (bf16 on the matrix cores for
+ *                  SGF_BF16 as sgf_combine_fc_bwd does, fp64-accumulated FMAs for SGF_F32).
+ *   workspace: sgf_head_rows_bwd_workspace_bytes(m, d, classes).  m == 0: all-zero gradients.
+ * Both entries need n < 2^31.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_head_rows_supported(int32_t d, int32_t classes, int32_t dtype);
+size_t sgf_head_rows_fwd_workspace_bytes(int64_t m);
+size_t sgf_head_rows_bwd_workspace_bytes(int64_t m, int32_t d, int32_t classes);
+int sgf_head_rows_fwd(const void* x1, int64_t ld1, float a, const void* x2, int64_t ld2, float b, const float* w,
+                      const float* bias, int64_t n, int32_t d, int32_t classes, int32_t dtype, const int64_t* idx,
+                      int64_t m, float* logits, int64_t ldl, const int64_t* labels, float* lse, float* loss_sum,
+                      int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int sgf_head_rows_bwd(const void* x1, int64_t ld1, float a, const void* x2, int64_t ld2, float b, const float* w,
+                      int64_t n, int32_t d, int32_t classes, int32_t dtype, const int64_t* idx, int64_t m,
+                      const float* dlogits, int64_t lddl, const float* logits, int64_t ldl, const float* lse,
+                      const int64_t* labels, const float* gout, float inv_denom, void* dx1, int64_t ldd1, void* dx2,
+                      int64_t ldd2, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

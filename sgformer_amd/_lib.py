@@ -189,6 +189,14 @@ SIGNATURES = {
     "sgf_argmax_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_argmax_count": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P,
                                    c_size_t, _P]),
+    "sgf_head_rows_supported": (c_int32, [c_int32, c_int32, c_int32]),
+    "sgf_head_rows_fwd_workspace_bytes": (c_size_t, [c_int64]),
+    "sgf_head_rows_bwd_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "sgf_head_rows_fwd": (c_int32, [_P, c_int64, c_float, _P, c_int64, c_float, _P, _P, c_int64, c_int32, c_int32, c_int32,
+                                    _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "sgf_head_rows_bwd": (c_int32, [_P, c_int64, c_float, _P, c_int64, c_float, _P, c_int64, c_int32, c_int32, c_int32,
+                                    _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_float, _P, c_int64, _P, c_int64,
+                                    _P, _P, _P, c_size_t, _P]),
     "sgf_sum_n": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64, _P]),
     "sgf_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_colsum": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P]),

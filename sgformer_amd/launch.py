@@ -29,6 +29,9 @@ cover; tests/test_launch_patches.py drives each with callers that are not the re
     F.log_softmax / F.nll_loss          lazy log-softmax + one-pass loss on the training rows   --sgf-aten-loss 1
     F.binary_cross_entropy_with_logits  nn.BCEWithLogitsLoss() of the multi-label sets in one pass
                                         (inputs of >= 2^23 elements; smaller ones stay on ATen)  --sgf-aten-loss 1
+    F.cross_entropy                     nn.CrossEntropyLoss() on the seed rows of a sampled batch (100M/nb-sample.py):
+                                        head, loss and gradient on those rows only.  Acts on the lazy rows the
+                                        model returns under SGF_SEED_HEAD=1 (default 0) and on nothing else  --sgf-aten-loss 1
     torch.optim.Adam.__init__           fused=True for all-CUDA float parameters                SGF_FUSED_ADAM=0
     torch_geometric.utils.subgraph      device implementation (main-batch.py only)              --sgf-host-subgraph 1
     torch_geometric.utils.to_undirected / remove_self_loops / add_self_loops                    --sgf-host-prologue 1
@@ -298,6 +301,40 @@ def unpatch_bce_loss():
         F.binary_cross_entropy_with_logits = orig
 
 
+def patch_ce_loss():
+    """The neighbour-sampled trainer keeps its two lines (100M/nb-sample.py:29-30 and :41-42):
+    `output = model(graph.x, graph.edge_index)[:batch_size]` and `nn.CrossEntropyLoss()(output, graph.y[:batch_size])`.
+    With SGF_SEED_HEAD=1 the model answers a sampled batch with a lazy head and `[:batch_size]` with lazy rows
+    (sgformer_amd.head_rows.LazyHead); this hook, installed behind torch.nn.functional.cross_entropy — which
+    nn.CrossEntropyLoss.forward looks up at call time — sends exactly that case to head_rows.cross_entropy: lazy rows that
+    nobody has read yet, a 1-D int64 target of class indices on their device, no class weights, no label smoothing,
+    reduction 'mean', ignore_index -100.  Every call on anything that is not lazy rows reaches the original untouched, and so
+    does every other call on lazy rows — with the real logits (the lazy object computes them).  `--sgf-aten-loss 1` keeps
+    ATen's.  Idempotent."""
+    import torch.nn.functional as F
+    from .head_rows import LazyHead, lazy_cross_entropy_ok
+    orig = getattr(F.cross_entropy, "_sgf_orig", F.cross_entropy)
+
+    def cross_entropy(input, target, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean",
+                      label_smoothing=0.0):
+        if type(input) is LazyHead and lazy_cross_entropy_ok(input, target, weight, size_average, ignore_index, reduce,
+                                                             reduction, label_smoothing):
+            return input._sgf_cross_entropy(target)
+        return orig(input, target, weight=weight, size_average=size_average, ignore_index=ignore_index, reduce=reduce,
+                    reduction=reduction, label_smoothing=label_smoothing)
+
+    cross_entropy._sgf_orig = orig
+    F.cross_entropy = cross_entropy
+    return orig
+
+
+def unpatch_ce_loss():
+    import torch.nn.functional as F
+    orig = getattr(F.cross_entropy, "_sgf_orig", None)
+    if orig is not None:
+        F.cross_entropy = orig
+
+
 # Rows from which each drop-in metric takes a call; below it — and always where the entry is None — the call goes to the
 # trainer's own function, so a patched trainer is never slower than an unpatched one.  A number here is a crossover
 # MEASURED by scripts/metrics_probe.py (profiles/metrics_probe.md: the original against the drop-in on host tensors, the
@@ -495,6 +532,7 @@ def main(argv=None):
     if aten_loss is None:
         patch_nll_loss()
         patch_bce_loss()
+        patch_ce_loss()
     patch_adam()
     if host_metrics is None:
         patch_eval_metrics(0 if device_metrics is not None else None)

@@ -36,6 +36,26 @@ def bce_with_logits_rows(out, target, train_idx, denom=None):
     return ops.bce_loss_rows(out, target, train_idx, denom)
 
 
+def cross_entropy_rows(model, x, edge_index, labels, rows):
+    """`nn.CrossEntropyLoss()(model(x, edge_index)[rows], labels[rows])` — 100M/nb-sample.py:29-30 with rows = batch_size —
+    without the other rows of the head: both branches of `model` (an SGFormer), then head, loss and gradient on the selected
+    rows only (sgformer_amd.head_rows, sgf_head_rows_fwd / _bwd).  `labels` is indexed by NODE id, [N] or [N, 1] as the
+    trainers keep it; `rows`: an int k (the first k nodes — the seeds of a sampled batch), an int64 index tensor or a bool
+    mask over the nodes.  Mean over the selected labels in [0, C); -100 and every other label outside the range are
+    ignored."""
+    n = x.shape[0]
+    labels = labels.reshape(-1)
+    if labels.numel() != n:
+        raise ValueError(f"cross_entropy_rows: labels must hold one class index per node ({n}), got {tuple(labels.shape)}")
+    if isinstance(rows, int) and not isinstance(rows, bool):
+        picked = labels[:rows]
+    elif _torch.is_tensor(rows):
+        picked = labels[rows.to(labels.device)]
+    else:
+        raise TypeError(f"cross_entropy_rows: rows must be an int, an int64 index tensor or a bool mask, got {type(rows).__name__}")
+    return model._forward(x, edge_index, rows, ce_labels=picked.to(_torch.int64))
+
+
 def dense_bce(input, target):
     """F.binary_cross_entropy_with_logits(input, target) — no weights, reduction 'mean' — for a 2-D input and a floating
     target of its shape, as ONE pass forward and one backward (the dense form of sgf_bce_fwd / _bwd) instead of ATen's

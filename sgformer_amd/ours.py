@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import head_rows, ops
 
 __all__ = ["GraphConvLayer", "GraphConv", "TransConvLayer", "TransConv", "SGFormer",
            "full_attention_conv"]
@@ -620,12 +620,31 @@ class SGFormer(nn.Module):
         return out.to(x.device)
 
     def forward(self, x, edge_index):
-        if not x.is_cuda and ops.K.name == "hip" and not next(self.parameters()).is_cuda:
+        return self._forward(x, edge_index)
+
+    def forward_rows(self, x, edge_index, rows):
+        """forward(x, edge_index)[rows] as fp32-accumulated [m, C] logits without the other rows of the head (100M/
+        nb-sample.py:29 reads `[:batch_size]` of it): both branches as in forward, then sgformer_amd.head_rows.logits on
+        their outputs.  `rows`: an int k (the prefix 0..k-1), an int64 index tensor or a bool mask over the nodes, in the
+        caller's node order.  An index tensor costs a host read per call (its range; whether its rows are distinct is read
+        once per tensor and cached — repeated rows take the existing operators on the gathered rows); an int and a mask do
+        not.  Not available node-sharded."""
+        if isinstance(rows, bool) or not (isinstance(rows, int) or torch.is_tensor(rows)):
+            raise TypeError(f"forward_rows: rows must be an int, an int64 index tensor or a bool mask, got {type(rows).__name__}")
+        return self._forward(x, edge_index, rows)
+
+    def _forward(self, x, edge_index, rows=None, ce_labels=None):
+        if rows is None and not x.is_cuda and ops.K.name == "hip" and not next(self.parameters()).is_cuda:
             return self._forward_on_gpu_from_host(x, edge_index)
         ops._require_cuda(x, edge_index)
         out_dtype = x.dtype if getattr(self, 'logits_dtype', None) is None else self.logits_dtype
         cdt = self.compute_dtype if self.compute_dtype is not None else x.dtype
-        if ops.hints_of(edge_index).csr is not None:
+        # a neighbour-sampled batch says how many of its rows are seeds (sampling.NeighborSampler): with SGF_SEED_HEAD=1 the
+        # head is not run here — the trainer's `[:batch_size]` and its loss decide which rows are needed (head_rows.LazyHead)
+        seeds = getattr(edge_index, "_sgf_seed_count", None) if rows is None else None
+        if seeds is not None and not head_rows.seed_head_enabled():
+            seeds = None
+        if rows is None and ops.hints_of(edge_index).csr is not None:
             # a mini-batch whose CSR came with its edge list (batching.subgraph): batches of one node count replay ONE captured
             # hipGraph per direction instead of ~150 launches (sgformer_amd/graphed.py; SGF_BATCH_GRAPH=0 turns it off)
             from . import graphed
@@ -677,7 +696,25 @@ class SGFormer(nn.Module):
                 hit = (key, xe, x)
                 holder._x_cache = hit
             x = hit[1]
-        return self._core(x, edge_index, view, repart, out_dtype)
+        if rows is not None or seeds is not None:
+            if repart is not None or shard is not None:
+                if rows is not None:
+                    raise NotImplementedError("sgformer_amd: forward_rows is not available on the node-sharded path")
+                seeds = None
+            elif torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                seeds = None
+            elif perm is not None:
+                if rows is None:
+                    seeds = None                     # (does not occur for sampled batches: today's head)
+                else:
+                    # the branches run in the view's node order: caller row r is module row inv[r]
+                    if isinstance(rows, int):
+                        if not 0 <= rows <= x.shape[0]:
+                            raise IndexError(f"forward_rows: a prefix of {rows} rows of {x.shape[0]}")
+                        rows = view.inv[:rows].long()
+                    else:
+                        rows = view.inv.long()[rows.to(view.inv.device)]
+        return self._core(x, edge_index, view, repart, out_dtype, rows=rows, lazy_seeds=seeds, ce_labels=ce_labels)
 
     def _entry_copy_uncached(self, x, cdt):
         """The entry copy for ONE use of x (a mini-batch's features): zero-padding to a multiple of 4 columns and the
@@ -688,7 +725,7 @@ class SGFormer(nn.Module):
             return ops.K.pad_rows(x, None, fp, cdt)
         return x if x.dtype == cdt else x.to(cdt)
 
-    def _core(self, x, edge_index, view, repart, out_dtype):
+    def _core(self, x, edge_index, view, repart, out_dtype, rows=None, lazy_seeds=None, ce_labels=None):
         """Everything between the entry copy and the logits: stems, both branches, combine + head (large/ours.py:265-276).
         `edge_index`: the reference's tensor, or an object with the CSR arrays (ops.CSRGraph, graphed.StaticCSR)."""
         # K10: the first Linear of both branches reads the same x — one pass, two outputs, the GCN stem's BatchNorm
@@ -738,6 +775,25 @@ class SGFormer(nn.Module):
         else:
             x1 = trans_branch()
             x2 = graph_branch() if self.use_graph else None
+        if rows is not None or lazy_seeds is not None:
+            # the head on selected rows: the operands in the order the full head takes them (below)
+            gw = float(self.graph_weight)
+            if not self.use_graph:
+                ha, hb, a, b = x1, None, 1.0, 0.0
+            elif self.aggregate == 'add':
+                ha, hb, a, b = x2, x1, gw, 1.0 - gw
+            else:
+                ha, hb, a, b = x1, x2, 1.0, 1.0       # 'cat': fc([x1 | x2]), head_rows reads it off the width of W
+            if ce_labels is not None:           # loss.cross_entropy_rows: the mean cross-entropy of those rows, fp32
+                return head_rows.cross_entropy(ha, hb, self.fc.weight, self.fc.bias, a, b, rows, ce_labels)
+            if rows is not None:
+                return head_rows.logits(ha, hb, self.fc.weight, self.fc.bias, a, b, rows).to(out_dtype)
+            return head_rows.LazyHead(ha, hb, self.fc, a, b, lambda: self._head(x1, x2, view, repart, out_dtype), out_dtype,
+                                      lazy_seeds)
+        return self._head(x1, x2, view, repart, out_dtype)
+
+    def _head(self, x1, x2, view, repart, out_dtype):
+        """Combine + fc on every row (large/ours.py:269-276), back in the caller's node order."""
         if self.use_graph and self.aggregate == 'add' and ops.combine_fc_supported(x1, self.fc.out_features):
             # gw * x2 + (1 - gw) * x1 -> fc in ONE kernel (large/ours.py:269-270,275): the combined
             # activations are never written, the logits come out in fp32

@@ -25,6 +25,15 @@ from . import _lib, ops
 from .kernels import _launch, _scratch
 
 
+def _seed_rows(edge_index, count):
+    """Record with a sampled edge list that the first `count` nodes of its batch are the seeds — the only rows whose logits the
+    trainer reads (100M/nb-sample.py:29, :41).  An attribute of the tensor next to the hint record, not a field of it:
+    SGFormer.forward reads it when SGF_SEED_HEAD=1 (head_rows.LazyHead); nothing else does."""
+    if count is not None:
+        edge_index._sgf_seed_count = int(count)
+    return edge_index
+
+
 class SampledBatch:
     """What the trainer reads off a NeighborLoader batch (100M/nb-sample.py:172-175,27-45): x, edge_index, y,
     batch_size, n_id; `.to(device)` is a no-op for tensors that are already there."""
@@ -40,6 +49,7 @@ class SampledBatch:
         if out.edge_index is not self.edge_index:
             # what ops.CSRGraph reads off a sampled edge list (the batch's CSR moves with it)
             ops.hints_of(self.edge_index).to(dev).attach(out.edge_index)
+            _seed_rows(out.edge_index, getattr(self.edge_index, "_sgf_seed_count", None))
         return out
 
 
@@ -141,7 +151,7 @@ class NeighborSampler:
         _launch(dev, "sgf_neighbor_sample_mark", self.local_of, n_id32, int(n_id32.numel()), -1)
         ei = torch.stack([torch.cat(srcs), torch.cat(dsts)]).long() if srcs else torch.zeros(2, 0, dtype=torch.int64, device=dev)
         # local ids are in range by construction: ops.CSRGraph skips its host check
-        return n_id32.long(), ops.EdgeHints(trusted=True).attach(ei), bs
+        return n_id32.long(), _seed_rows(ops.EdgeHints(trusted=True).attach(ei), bs), bs
 
     def _batch_capacity(self, bs: int) -> int:
         """Worst-case number of sampled entries of one batch: bs * (k1 + k1 k2 + ...)."""
@@ -184,7 +194,7 @@ class NeighborSampler:
         # every node is a frontier node once: at most fan-out in-edges; ops.CSRGraph adopts the CSR and transposes it with
         # sgf_sampled_csr_transpose (no symmetry test, no host read)
         hints = ops.EdgeHints(trusted=True, max_in_degree=max(self.fanouts), csr=csr, csr_t_lazy=csr is not None)
-        return nodes[:nn].long(), hints.attach(ei), bs
+        return nodes[:nn].long(), _seed_rows(hints.attach(ei), bs), bs
 
     def _hops(self, nodes, srcs, dsts, frontier, local0, n_known, batch_id):
         """The hop-by-hop path (a fan-out of -1 has no a-priori capacity): one sgf_neighbor_sample_hop per hop, its edge and
