@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 665 /* 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 666 /* 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -1121,6 +1121,51 @@ int sgf_head_rows_bwd(const void* x1, int64_t ld1, float a, const void* x2, int6
                       const float* dlogits, int64_t lddl, const float* logits, int64_t ldl, const float* lse,
                       const int64_t* labels, const float* gout, float inv_denom, void* dx1, int64_t ldd1, void* dx2,
                       int64_t ldd2, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N7 — DIFFormer's all-pair sigmoid attention (medium/difformer.py:41-52, kernel='sigmoid') as tiled products: no n x l
+ * tensor is formed, the scores live in registers.  Per head, with z = q_i . k_j and S = sigmoid(z):
+ *     r_i = sum_j S          out_i = sum_j S v_j / r_i                                   (sgf_pair_sigmoid_fwd)
+ *     delta_i = g_i . out_i  dZ = S (1 - S) (g_i . v_j - delta_i) / r_i   dq_i = sum_j dZ k_j   (sgf_pair_sigmoid_bwd_q)
+ *     dv_j = sum_i (S / r_i) g_i                                          dk_j = sum_i dZ q_i   (sgf_pair_sigmoid_bwd_kv)
+ * Operands, row-major, leading dimensions in elements, rows 16-byte aligned: q / g / out / dq [n, heads * d], k / dk
+ * [l, heads * d], v / dv [l, v_heads * d] with v_heads == heads, or v_heads == 1 for one value head that every head shares
+ * (dv is then the sum over the heads, formed inside the kernel in head order); rowsum fp32 [n, heads] (= r).
+ * Shapes (sgf_pair_sigmoid_supported): d in {32, 64, 128}, 1 <= heads <= 8, SGF_F32 or SGF_BF16; anything else, and
+ * SGF_F32_BF16X3, is SGF_E_UNSUPPORTED (fp32 tensors run the exact kernel under every matmul-precision setting).  n and l
+ * are arbitrary (< 2^31); a key past l adds exactly 0 (it is masked, not zero-filled: sigmoid(0) = 0.5), rows past n are
+ * never stored.  z >= 17 gives S = 1, z <= -104 gives S = 0, and 1 - S is formed from S: a saturated pair has an exactly
+ * zero dZ.  No NaN comes out of the exponential's overflow.
+ *   SGF_BF16: z and g . v on v_mfma_f32_32x32x16_bf16 with fp32 accumulators; the sigmoid, r, delta and 1 / r in fp32; S
+ *     (fwd), S / r and dZ (bwd) are rounded to bf16 only as operands of the second products — rowsum is the fp32 sum of the
+ *     unrounded S; out = sum_j S~ v_j / sum_j S~ with S~ the rounded S (a convex combination of the value rows), divided in
+ *     fp32 and rounded once.
+ *   SGF_F32: v_mfma_f32_32x32x2_f32, exact fp32 products; S and dZ are used as they are.
+ * Every result is a fixed-order sum inside one workgroup: fwd / bwd_q keep 128 query rows resident and sweep the keys,
+ * bwd_kv keeps 128 keys resident and sweeps the queries; both backward launches recompute S.  No atomics: bit-reproducible.
+ * sgf_pair_sigmoid_bwd_q leaves delta fp32 [n, heads] in `workspace` (sgf_pair_sigmoid_workspace_bytes(n, l, heads) =
+ * 4 n heads bytes), where sgf_pair_sigmoid_bwd_kv reads it: call bwd_q first (dq == NULL: delta only, no sweep).
+ * Checks, all before the first HIP call: v_heads not in {1, heads}, a null pointer, l == 0 with n > 0, a leading dimension
+ * below the operand's width or one that breaks the 16-byte row alignment: SGF_E_INVALID.  n == 0: SGF_OK, no launch,
+ * nothing is written.
+ * sgf_pair_sigmoid_lap_rows(which, ...) (which: 0 fwd, 1 bwd_q, 2 bwd_kv; the counterpart of sgf_row_lap_rows): the
+ * smallest n (bwd_kv: l) at which every workgroup walks at least `laps` resident tiles; 0 = one tile per workgroup
+ * (all three kernels today), -1 for an unsupported shape.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_pair_sigmoid_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype);
+size_t sgf_pair_sigmoid_workspace_bytes(int64_t n, int64_t l, int32_t heads);
+int64_t sgf_pair_sigmoid_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps);
+int sgf_pair_sigmoid_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n,
+                         int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* out, int64_t ldo,
+                         float* rowsum, void* stream);
+int sgf_pair_sigmoid_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* rowsum, const void* q,
+                           int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                           int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dq, int64_t lddq, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* rowsum, const void* q, int64_t ldq, const void* k,
+                            int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
+                            int32_t d, int32_t dtype, void* dk, int64_t lddk, void* dv, int64_t lddv, const void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

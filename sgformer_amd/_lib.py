@@ -197,6 +197,15 @@ SIGNATURES = {
     "sgf_head_rows_bwd": (c_int32, [_P, c_int64, c_float, _P, c_int64, c_float, _P, c_int64, c_int32, c_int32, c_int32,
                                     _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_float, _P, c_int64, _P, c_int64,
                                     _P, _P, _P, c_size_t, _P]),
+    "sgf_pair_sigmoid_supported": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    "sgf_pair_sigmoid_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "sgf_pair_sigmoid_lap_rows": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "sgf_pair_sigmoid_fwd": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                       c_int32, _P, c_int64, _P, _P]),
+    "sgf_pair_sigmoid_bwd_q": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int64,
+                                         c_int64, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_size_t, _P]),
+    "sgf_pair_sigmoid_bwd_kv": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int32,
+                                          c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_size_t, _P]),
     "sgf_sum_n": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64, _P]),
     "sgf_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_colsum": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P]),

@@ -1,0 +1,519 @@
+// pair_attn.hip — DIFFormer's all-pair sigmoid attention (medium/difformer.py:41-52, kernel='sigmoid') without the
+// n x l score tensor (include/sgf.h block N7).  With z = q_i . k_j and S = sigmoid(z), per head:
+//
+//   sgf_pair_sigmoid_fwd    : r_i = sum_j S,  out_i = sum_j S v_j / r_i
+//   sgf_pair_sigmoid_bwd_q  : delta_i = g_i . out_i,  dZ = S (1 - S) (g_i . v_j - delta_i) / r_i,  dq_i = sum_j dZ k_j
+//   sgf_pair_sigmoid_bwd_kv : dv_j = sum_i (S / r_i) g_i,  dk_j = sum_i dZ q_i
+//
+// The scores are bounded, so there is no running maximum and no rescale: a flash-style sweep with plain sums.
+//
+// gfx950 mapping.  A workgroup is 4 waves; it keeps 128 rows resident (32 per wave: queries in fwd / bwd_q, keys in
+// bwd_kv) and sweeps the other side in LDS tiles that all four waves share.  Nothing is summed across workgroups: no
+// atomics, no hand-off, every result is a fixed-order sum (bwd_q and bwd_kv both recompute S: seven products, not five).
+//   * The first products (z, and g . v in the backward) put the RESIDENT row on the MFMA lane and the swept row in the 16
+//     accumulator registers: X[swept][resident].  The second products sum over the swept row, which is X's row index, so
+//     the accumulator tile is the next MFMA's B operand as it stands (no lane movement, no LDS round trip): per lane the
+//     row constants r_i / delta_i are scalars (fwd, bwd_q) or two LDS broadcasts per register (bwd_kv).
+//   * bf16 storage: v_mfma_f32_32x32x16_bf16.  Registers 8s .. 8s+7 of X, converted pairwise, are k-step s of the B
+//     operand; element j of lane half h is then X's row 16s + 8(j>>2) + 4h + (j&3).  The swept rows are assigned to X's rows
+//     with bits 2 and 3 swapped (swap23), which makes that k order the natural one: the A operand of the second product
+//     is one 16-byte read of a transposed LDS image [feature][swept row].  The tile is staged twice, row-major for the
+//     first product and transposed for the second.
+//   * fp32 storage: v_mfma_f32_32x32x2_f32 (exact fp32 products, one operand register per lane): register q of X is the B
+//     operand of one MFMA whose two k are X's rows of the two lane halves; the A operand is a 4-byte read of the
+//     row-major image, so one image serves both products.  S and dZ are used unrounded.
+//   * sigmoid: u = exp(-z), S = 1 / (1 + u) in fp32.  z >= 17: 1 + u rounds to 1, S = 1.  z <= -88.8: u = inf, S = 0 (no
+//     NaN: nothing is multiplied by u).  1 - S is formed from S, so a saturated score has an exactly zero derivative.
+//   * tails: a swept row past the end is staged as zeros AND masked (a zero key would score sigmoid(0) = 0.5): keys by a
+//     compare on the row index, queries (bwd_kv) by a staged 1 / r = 0.  Resident rows past the end are clamped for the
+//     loads and never stored.
+#include "common.h"
+
+namespace sgf {
+namespace {
+
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kPaThreads = 256;                  // 4 waves
+constexpr int kPaRows = 32 * (kPaThreads / 64);  // resident rows per workgroup
+
+struct PaArgs {
+  const void *q, *k, *v, *g, *o;   // o: the forward's out (bwd_q)
+  int64_t ldq, ldk, ldv, ldg, ldo;
+  void *out, *dq, *dk, *dv;
+  int64_t ldout, lddq, lddk, lddv;
+  float* rowsum;                   // [n, heads]: written by fwd, read by the backward
+  float* delta;                    // [n, heads]: written by bwd_q, read by bwd_kv
+  int64_t n, l;
+  int heads, v_heads;
+};
+
+__device__ __forceinline__ int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
+// swept row (inside a 32-row sub-tile) that register q of lane half hh holds: swap23 of the MFMA's C/D row
+__device__ __forceinline__ int slot_of(int q, int hh) { return (q & 3) + 4 * ((q >> 2) & 1) + 8 * hh + 16 * (q >> 3); }
+
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  const f32x2_t v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));   // v_cvt_pk_bf16_f32, round to nearest even
+}
+
+// S = sigmoid(z).  fp32 storage: expf; bf16 storage: the hardware exp2 (S is rounded to 8 bits right after)
+template <bool kExact>
+__device__ __forceinline__ float sigmoid(float z) {
+  const float u = kExact ? expf(-z) : __builtin_amdgcn_exp2f(-1.44269504088896341f * z);
+  return __builtin_amdgcn_rcpf(1.0f + u);
+}
+
+// One swept tile of SW rows x D features in LDS: `rm` row-major (pitch D + pad), `tr` transposed [feature][row] (bf16 only).
+template <typename T, int D, int SW>
+struct PaImg {
+  static constexpr bool kBf16 = std::is_same<T, uint16_t>::value;
+  static constexpr int kVec = 16 / static_cast<int>(sizeof(T));
+  static constexpr int kPitch = D + (kBf16 ? 8 : 4);
+  static constexpr int kPitchT = SW + 8;
+  static constexpr int kRm = SW * kPitch;
+  static constexpr int kTr = kBf16 ? D * kPitchT : 4;
+  static constexpr int kFrags = kBf16 ? D / 16 : D / 2;
+  using Frag = typename std::conditional<kBf16, bf16x8, float>::type;
+
+  // rows row0 .. row0 + SW - 1 of src (already at the head's first column); rows >= nrows are zeros
+  template <bool RM, bool TR>
+  static __device__ __forceinline__ void stage(const T* __restrict__ src, int64_t ld, int64_t row0, int64_t nrows, T* rm,
+                                               T* tr) {
+    constexpr int CH = D / kVec;
+    for (int idx = threadIdx.x; idx < SW * CH; idx += kPaThreads) {
+      const int row = idx % SW, c = idx / SW;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (row0 + row < nrows) v = *reinterpret_cast<const uint4*>(src + (row0 + row) * ld + kVec * c);
+      if constexpr (RM) *reinterpret_cast<uint4*>(rm + row * kPitch + kVec * c) = v;
+      if constexpr (TR && kBf16) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          tr[(8 * c + 2 * e) * kPitchT + row] = static_cast<T>(w[e] & 0xffffu);
+          tr[(8 * c + 2 * e + 1) * kPitchT + row] = static_cast<T>(w[e] >> 16);
+        }
+      }
+    }
+  }
+
+  // the resident row's fragments (B operand of the first products): row points at the head's first column of that row
+  static __device__ __forceinline__ void load_frags(const T* __restrict__ row, int hh, Frag* f) {
+    if constexpr (kBf16) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) f[s] = *reinterpret_cast<const bf16x8*>(row + 16 * s + 8 * hh);
+    } else {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) f[s] = row[2 * s + hh];
+    }
+  }
+
+  // this lane's share of frags . row (the other lane half holds the rest)
+  static __device__ __forceinline__ float dot_frags(const Frag* f, const T* __restrict__ row, int hh) {
+    float acc = 0.f;
+    if constexpr (kBf16) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) {
+        const bf16x8 o = *reinterpret_cast<const bf16x8*>(row + 16 * s + 8 * hh);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc = fmaf(bf16_to_f32(static_cast<uint16_t>(f[s][j])), bf16_to_f32(static_cast<uint16_t>(o[j])), acc);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) acc = fmaf(f[s], row[2 * s + hh], acc);
+    }
+    return acc;
+  }
+
+  // X[swept row][resident row] = sum over the features, sub-tile st: lane r reads LDS row swap23(r)
+  static __device__ __forceinline__ f32x16 dot(const T* rm, int st, int r, int hh, const Frag* b) {
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    const T* a = rm + (32 * st + swap23(r)) * kPitch + (kBf16 ? 8 * hh : hh);
+    if constexpr (kBf16) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(a + 16 * s), b[s], acc, 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2 * s], b[s], acc, 0, 0, 0);
+    }
+    return acc;
+  }
+
+  // out[t][feature 32 t + .][resident row] += sum over the swept rows of image[row][feature] x[row][resident row]
+  static __device__ __forceinline__ void acc(const T* rm, const T* tr, int st, const f32x16& x, f32x16* out, int r, int hh) {
+    if constexpr (kBf16) {
+      union {
+        bf16x8 v;
+        uint32_t u[4];
+      } xb[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xb[s].u[i] = pk_bf16(x[8 * s + 2 * i], x[8 * s + 2 * i + 1]);
+#pragma unroll
+      for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const bf16x8 a = *reinterpret_cast<const bf16x8*>(tr + (32 * t + r) * kPitchT + 32 * st + 16 * s + 8 * hh);
+          out[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[s].v, out[t], 0, 0, 0);
+        }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const T* a = rm + (32 * st + slot_of(q, hh)) * kPitch + r;
+#pragma unroll
+        for (int t = 0; t < D / 32; ++t) out[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[32 * t], x[q], out[t], 0, 0, 0);
+      }
+    }
+  }
+
+  // features 32 t + 8 g + 4 hh .. + 3 of this lane's resident row, as 4-element stores
+  template <bool DIV>
+  static __device__ __forceinline__ void store(T* __restrict__ row, const f32x16* a, int hh, float den) {
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float4 v = make_float4(a[t][4 * g], a[t][4 * g + 1], a[t][4 * g + 2], a[t][4 * g + 3]);
+        if constexpr (DIV) v = make_float4(v.x / den, v.y / den, v.z / den, v.w / den);
+        store4<T>(row + 32 * t + 8 * g + 4 * hh, v);
+      }
+  }
+};
+
+// swept rows per stage: two sub-tiles where the LDS images stay below 64 KiB
+template <typename T, int WHICH>
+constexpr int pa_sweep() { return std::is_same<T, uint16_t>::value && WHICH != 2 ? 64 : 32; }
+
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads) void k_pa_fwd(const PaArgs p) {
+  constexpr int SW = pa_sweep<T, 0>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) T vs[I::kBf16 ? 4 : I::kRm];
+  __shared__ __attribute__((aligned(16))) T vt[I::kTr];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t ic = i < p.n ? i : p.n - 1;
+  const T* kp = static_cast<const T*>(p.k) + h * D;
+  const T* vp = static_cast<const T*>(p.v) + hv * D;
+  typename I::Frag qf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
+  f32x16 o[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) o[t][q] = 0.f;
+  float rs = 0.f, den = 0.f;
+  for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
+    I::template stage<true, false>(kp, p.ldk, j0, p.l, ks, nullptr);
+    I::template stage<!I::kBf16, true>(vp, p.ldv, j0, p.l, vs, vt);
+    __syncthreads();
+#pragma unroll
+    for (int st = 0; st < SW / 32; ++st) {
+      const int64_t lim = p.l - j0 - 32 * st;        // swept rows of this sub-tile that exist
+      if (lim > 0) {                                 // (workgroup-uniform)
+        f32x16 x = I::dot(ks, st, r, hh, qf);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float s = slot_of(q, hh) < lim ? sigmoid<!I::kBf16>(x[q]) : 0.f;
+          rs += s;                                   // r: fp32, before the operand's rounding to bf16
+          if constexpr (I::kBf16) den += __uint_as_float(pk_bf16(s, 0.f) << 16);   // what the numerator's weights sum to
+          x[q] = s;
+        }
+        I::acc(vs, vt, st, x, o, r, hh);
+      }
+    }
+    __syncthreads();
+  }
+  rs += __shfl_xor(rs, 32, 64);
+  // bf16: the numerator holds the ROUNDED weights, so it is divided by their sum — out stays a convex combination of the
+  // value rows (one key: out = v exactly), which is what keeps g . v - delta free of rounding noise in the backward
+  den = I::kBf16 ? den + __shfl_xor(den, 32, 64) : rs;
+  if (i < p.n) {
+    I::template store<true>(static_cast<T*>(p.out) + i * p.ldout + h * D, o, hh, den);
+    if (hh == 0) p.rowsum[i * p.heads + h] = rs;
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads) void k_pa_bwd_q(const PaArgs p) {
+  constexpr int SW = pa_sweep<T, 1>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) T vs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T kt[I::kTr];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t ic = i < p.n ? i : p.n - 1;
+  const T* kp = static_cast<const T*>(p.k) + h * D;
+  const T* vp = static_cast<const T*>(p.v) + hv * D;
+  typename I::Frag qf[I::kFrags], gf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.g) + ic * p.ldg + h * D, hh, gf);
+  float delta = I::dot_frags(gf, static_cast<const T*>(p.o) + ic * p.ldo + h * D, hh);
+  delta += __shfl_xor(delta, 32, 64);
+  if (i < p.n && hh == 0) p.delta[i * p.heads + h] = delta;
+  if (!p.dq) return;                                 // (uniform: delta only)
+  I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
+  const float rinv = 1.0f / p.rowsum[ic * p.heads + h];
+  f32x16 dq[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dq[t][q] = 0.f;
+  for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
+    I::template stage<true, true>(kp, p.ldk, j0, p.l, ks, kt);
+    I::template stage<true, false>(vp, p.ldv, j0, p.l, vs, nullptr);
+    __syncthreads();
+#pragma unroll
+    for (int st = 0; st < SW / 32; ++st) {
+      const int64_t lim = p.l - j0 - 32 * st;
+      if (lim > 0) {
+        f32x16 x = I::dot(ks, st, r, hh, qf);
+        const f32x16 pv = I::dot(vs, st, r, hh, gf);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float s = sigmoid<!I::kBf16>(x[q]);
+          const float dz = s * (1.0f - s) * ((pv[q] - delta) * rinv);
+          x[q] = slot_of(q, hh) < lim ? dz : 0.f;
+        }
+        I::acc(ks, kt, st, x, dq, r, hh);
+      }
+    }
+    __syncthreads();
+  }
+  if (i < p.n) I::template store<false>(static_cast<T*>(p.dq) + i * p.lddq + h * D, dq, hh, 1.f);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads) void k_pa_bwd_kv(const PaArgs p) {
+  constexpr int SW = pa_sweep<T, 2>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T qs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T gs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T qt[I::kTr];
+  __shared__ __attribute__((aligned(16))) T gt[I::kTr];
+  __shared__ float rinv_s[SW], delta_s[SW];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const bool shared_v = p.v_heads != p.heads;        // one value head: this workgroup walks every head, dv sums over them
+  const int h_begin = shared_v ? 0 : blockIdx.y, h_end = shared_v ? p.heads : h_begin + 1;
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t jc = j < p.l ? j : p.l - 1;
+  typename I::Frag kf[I::kFrags], vf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.v) + jc * p.ldv + (shared_v ? 0 : h_begin) * D, hh, vf);
+  f32x16 dk[D / 32], dv[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dv[t][q] = 0.f;
+  for (int h = h_begin; h < h_end; ++h) {
+    I::load_frags(static_cast<const T*>(p.k) + jc * p.ldk + h * D, hh, kf);
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dk[t][q] = 0.f;
+    const T* qp = static_cast<const T*>(p.q) + h * D;
+    const T* gp = static_cast<const T*>(p.g) + h * D;
+    for (int64_t i0 = 0; i0 < p.n; i0 += SW) {
+      I::template stage<true, true>(qp, p.ldq, i0, p.n, qs, qt);
+      I::template stage<true, true>(gp, p.ldg, i0, p.n, gs, gt);
+      if (threadIdx.x < SW) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < p.n;
+        rinv_s[threadIdx.x] = in ? 1.0f / p.rowsum[i * p.heads + h] : 0.f;     // 0: a query row past the end adds nothing
+        delta_s[threadIdx.x] = in ? p.delta[i * p.heads + h] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int st = 0; st < SW / 32; ++st) {
+        if (p.n - i0 - 32 * st > 0) {
+          f32x16 x = I::dot(qs, st, r, hh, kf);
+          f32x16 pv = I::dot(gs, st, r, hh, vf);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const int sl = 32 * st + slot_of(q, hh);
+            const float ri = rinv_s[sl], de = delta_s[sl];
+            const float s = sigmoid<!I::kBf16>(x[q]);
+            x[q] = s * ri;
+            pv[q] = s * (1.0f - s) * ((pv[q] - de) * ri);
+          }
+          I::acc(gs, gt, st, x, dv, r, hh);
+          I::acc(qs, qt, st, pv, dk, r, hh);
+        }
+      }
+      __syncthreads();
+    }
+    if (j < p.l) {
+      I::template store<false>(static_cast<T*>(p.dk) + j * p.lddk + h * D, dk, hh, 1.f);
+      if (!shared_v) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv + h * D, dv, hh, 1.f);
+    }
+  }
+  if (shared_v && j < p.l) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv, dv, hh, 1.f);
+}
+
+inline bool pa_shape_ok(int heads, int v_heads, int d, int dtype) {
+  if (dtype != SGF_F32 && dtype != SGF_BF16) return false;
+  if (d != 32 && d != 64 && d != 128) return false;
+  return heads >= 1 && heads <= 8 && (v_heads == 1 || v_heads == heads);
+}
+
+inline bool pa_aligned(const void* p, int64_t ld, int64_t per16) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % per16 == 0; }
+
+// sizes, head counts, width and dtype of all three launches
+int check_pa(const char* fn, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype) {
+  SGF_REQUIRE(n >= 0 && l >= 0, SGF_E_INVALID, "%s: negative size n=%lld l=%lld", fn, static_cast<long long>(n),
+              static_cast<long long>(l));
+  SGF_REQUIRE(v_heads == 1 || v_heads == heads, SGF_E_INVALID, "%s: v_heads=%d must be 1 or heads=%d", fn, v_heads, heads);
+  SGF_REQUIRE(pa_shape_ok(heads, v_heads, d, dtype), SGF_E_UNSUPPORTED,
+              "%s: needs d in {32, 64, 128}, 1 <= heads <= 8 and SGF_F32 or SGF_BF16 (heads=%d, d=%d, dtype %d)", fn, heads, d,
+              dtype);
+  SGF_REQUIRE(n < (static_cast<int64_t>(1) << 31) && l < (static_cast<int64_t>(1) << 31), SGF_E_UNSUPPORTED,
+              "%s: more than 2^31 - 1 rows", fn);
+  return SGF_OK;
+}
+
+struct PaOperand {
+  const char* name;
+  const void* p;
+  int64_t ld;
+  int width;
+};
+
+// null pointers, then the widths, then the alignment: all before the first HIP call
+int check_pa_rows(const char* fn, const PaOperand* ops, int count, int dtype) {
+  for (int i = 0; i < count; ++i) SGF_REQUIRE(ops[i].p, SGF_E_INVALID, "%s: null pointer (%s)", fn, ops[i].name);
+  for (int i = 0; i < count; ++i)
+    SGF_REQUIRE(ops[i].ld >= ops[i].width, SGF_E_INVALID, "%s: leading dimension smaller than the width (%s: %lld < %d)", fn,
+                ops[i].name, static_cast<long long>(ops[i].ld), ops[i].width);
+  const int per16 = dtype == SGF_BF16 ? 8 : 4;
+  for (int i = 0; i < count; ++i)
+    SGF_REQUIRE(pa_aligned(ops[i].p, ops[i].ld, per16), SGF_E_INVALID,
+                "%s: rows must be 16-byte aligned (pointers %% 16, leading dims %% %d elements; %s)", fn, per16, ops[i].name);
+  return SGF_OK;
+}
+
+template <template <typename, int> class Launch>
+int pa_dispatch(int d, int dtype, const PaArgs& a, dim3 grid, hipStream_t st) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (d == 32) Launch<T, 32>::run(a, grid, st);
+    else if (d == 64) Launch<T, 64>::run(a, grid, st);
+    else Launch<T, 128>::run(a, grid, st);
+    SGF_LAUNCH_CHECK();
+    return static_cast<int>(SGF_OK);
+  });
+}
+template <typename T, int D>
+struct PaFwd {
+  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_pa_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  }
+};
+template <typename T, int D>
+struct PaBwdQ {
+  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_pa_bwd_q<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  }
+};
+template <typename T, int D>
+struct PaBwdKv {
+  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_pa_bwd_kv<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  }
+};
+
+inline unsigned pa_tiles(int64_t rows) { return static_cast<unsigned>((rows + kPaRows - 1) / kPaRows); }
+
+}  // namespace
+}  // namespace sgf
+
+using namespace sgf;
+
+extern "C" int32_t sgf_pair_sigmoid_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype) {
+  return pa_shape_ok(heads, v_heads, d, dtype) ? 1 : 0;
+}
+
+// delta fp32 [n, heads]; nothing of size l, nothing of size n x l
+extern "C" size_t sgf_pair_sigmoid_workspace_bytes(int64_t n, int64_t l, int32_t heads) {
+  if (n < 0 || l < 0 || heads < 1) return 0;
+  return static_cast<size_t>(n) * heads * sizeof(float);
+}
+
+extern "C" int64_t sgf_pair_sigmoid_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
+  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
+    set_error("sgf_pair_sigmoid_lap_rows: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", which, laps,
+              heads, d, dtype);
+    return -1;
+  }
+  return 0;      // every workgroup of the three kernels owns one resident tile: there is no second lap
+}
+
+extern "C" int sgf_pair_sigmoid_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                    int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* out,
+                                    int64_t ldo, float* rowsum, void* stream) {
+  const char* fn = "sgf_pair_sigmoid_fwd";
+  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
+  const PaOperand ops[] = {{"q", q, ldq, heads * d}, {"k", k, ldk, heads * d}, {"v", v, ldv, v_heads * d}, {"out", out, ldo, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 4, dtype)) return rc;
+  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
+  PaArgs a = {};
+  a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv, a.out = out, a.ldout = ldo, a.rowsum = rowsum;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaFwd>(d, dtype, a, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sgf_pair_sigmoid_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* rowsum,
+                                      const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                      int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dq,
+                                      int64_t lddq, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "sgf_pair_sigmoid_bwd_q";
+  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"out", out, ldo, heads * d}, {"q", q, ldq, heads * d},
+                           {"k", k, ldk, heads * d},   {"v", v, ldv, v_heads * d},   {"dq", dq, lddq, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, dq ? 6 : 5, dtype)) return rc;      // dq == NULL: delta only
+  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
+  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_sigmoid_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
+              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
+              sgf_pair_sigmoid_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.o = out, a.ldo = ldo, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(rowsum), a.delta = static_cast<float*>(workspace), a.dq = dq, a.lddq = lddq;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaBwdQ>(d, dtype, a, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* rowsum, const void* q, int64_t ldq,
+                                       const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                                       int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dk, int64_t lddk,
+                                       void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "sgf_pair_sigmoid_bwd_kv";
+  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"q", q, ldq, heads * d},     {"k", k, ldk, heads * d},
+                           {"v", v, ldv, v_heads * d}, {"dk", dk, lddk, heads * d},  {"dv", dv, lddv, v_heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 6, dtype)) return rc;
+  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
+  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_sigmoid_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
+              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
+              sgf_pair_sigmoid_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(rowsum), a.delta = static_cast<float*>(const_cast<void*>(workspace));
+  a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaBwdKv>(d, dtype, a, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
+                              static_cast<hipStream_t>(stream));
+}

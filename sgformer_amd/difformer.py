@@ -6,8 +6,9 @@ place of `N * V_n` in the numerator, so it runs on `ops.attention_from_input(...
 of the layer input + d x d algebra + one apply pass; Q / K never materialised); `gcn_conv`
 (:63-79) is the same symmetric normalisation and sum-reduce SpMM as large/ours.py:26-34, applied to
 the projected V.  Same class names, constructor signatures, parameter names and creation order as
-the reference, so `state_dict`s interchange.  The O(N^2) `sigmoid` kernel and `output_attn` maps are
-plain PyTorch on the GPU, as in the reference.
+the reference, so `state_dict`s interchange.  The all-pair `sigmoid` kernel (DIFFormer-a) runs on the tiled kernels of
+pair_attn.py (no [N, L, H] score tensor) for head widths 32 / 64 / 128; the `output_attn` maps, other widths, the
+node-sharded case and `simple` with several heads are plain PyTorch on the GPU, as in the reference.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, pair_attn
 from .ours import _drop
 
 __all__ = ["DIFFormer", "DIFFormerConv", "full_attention_conv", "gcn_conv"]
@@ -65,8 +66,11 @@ def _dense_attention(qs, ks, vs, kernel, want_attn):
 
 
 def full_attention_conv(qs, ks, vs, kernel, output_attn=False):
-    """medium/difformer.py:10-61 as a free function on materialised Q / K / V (plain PyTorch; the
-    module's fast path goes through ops.attention_from_input instead)."""
+    """medium/difformer.py:10-61 as a free function on materialised Q / K / V (plain PyTorch, but for the sigmoid kernel
+    without the maps, which pair_attn takes where it can; the module's `simple` fast path goes through
+    ops.attention_from_input instead)."""
+    if kernel == 'sigmoid' and not output_attn and pair_attn.use_kernels(qs, ks, vs):
+        return pair_attn.sigmoid_attention(qs, ks, vs)
     out, attn = _dense_attention(qs, ks, vs, kernel, output_attn)
     return (out, attn) if output_attn else out
 
@@ -111,6 +115,8 @@ class DIFFormerConv(nn.Module):
             return out.unsqueeze(1), None
         q = ops.linear(x, self.Wq.weight, self.Wq.bias).reshape(n, h, d)
         k = ops.linear(x, self.Wk.weight, self.Wk.bias).reshape(n, h, d)
+        if self.kernel == 'sigmoid' and not output_attn and self._shard is None and pair_attn.use_kernels(q, k, value):
+            return pair_attn.sigmoid_attention(q, k, value), None
         return _dense_attention(q, k, value, self.kernel, output_attn)
 
     def forward(self, query_input, source_input, edge_index=None, edge_weight=None, x_0=None, output_attn=False):
