@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 666 /* 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 667 /* 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -1166,6 +1166,50 @@ int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* rowsum, con
                             int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
                             int32_t d, int32_t dtype, void* dk, int64_t lddk, void* dv, int64_t lddv, const void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N8 — the exact softmax all-pair attention (medium/ablation/oursSOFT.py, the "is linear attention enough?" ablation) on
+ * the skeleton of N7: no n x l tensor, the scores live in registers, with an online maximum.  Per head, with
+ * z = scale q_i . k_j:
+ *     m_i = max_j z   r_i = sum_j exp(z - m_i)   out_i = sum_j exp(z - m_i) v_j / r_i   lse_i = m_i + log r_i
+ *                                                                                            (sgf_pair_softmax_fwd)
+ *     P = exp(z - lse_i)   delta_i = g_i . out_i   dZ = scale P (g_i . v_j - delta_i)   dq_i = sum_j dZ k_j
+ *                                                                                            (sgf_pair_softmax_bwd_q)
+ *     dv_j = sum_i P g_i                                                 dk_j = sum_i dZ q_i   (sgf_pair_softmax_bwd_kv)
+ * Operands, layouts, leading dimensions, the 16-byte row alignment, v_heads in {heads, 1} (dv summed over the heads inside
+ * the kernel, in head order), the shapes (sgf_pair_softmax_supported: d in {32, 64, 128}, 1 <= heads <= 8, SGF_F32 or
+ * SGF_BF16; SGF_F32_BF16X3 is SGF_E_UNSUPPORTED), the workspace (delta fp32 [n, heads], written by bwd_q — dq == NULL:
+ * delta only — and read by bwd_kv), the checks and their order, and sgf_pair_softmax_lap_rows are those of N7.  The
+ * differences: `lse` fp32 [n, heads] stands where `rowsum` stood, and `scale` (after dtype) multiplies the scores; it must
+ * be finite and positive, else SGF_E_INVALID (checked after the shape, before the pointers and for an empty problem too).
+ * Online update, fp32, per swept stage: m' = max(m, stage max), c = exp(m - m'), r = c r + sum P, acc = c acc + P V.  m
+ * starts at -inf; the stage maximum is finite from the first stage on (the two lane halves exchange it before P is
+ * formed), so exp(-inf - (-inf)) is never evaluated.  A key past l is masked to -inf before the maximum: it takes no part
+ * in it and adds exactly 0 (zero-filling would score exp(0 - m)); rows past n are never stored.  z - m <= 0 always: for any
+ * finite scores, |z| of several thousand included, nothing overflows and no NaN or inf comes out; pairs that underflow
+ * contribute exactly 0.  The backward launches recompute P from lse and need no maximum.
+ *   SGF_BF16: z and g . v on v_mfma_f32_32x32x16_bf16 with fp32 accumulators, exp by the hardware exp2; m, r, lse, delta and
+ *     the rescale in fp32; P (fwd) and P, dZ (bwd) are rounded to bf16 only as operands of the second products — lse holds
+ *     the fp32 sum of the unrounded P; out = sum_j P~ v_j / sum_j P~ with P~ the rounded P (a convex combination of the
+ *     value rows), divided in fp32 and rounded once.
+ *   SGF_F32: v_mfma_f32_32x32x2_f32, exact fp32 products, expf; P and dZ are used as they are.
+ * Every result is a fixed-order sum inside one workgroup (128 resident rows, the other side swept): no atomics, nothing
+ * summed across workgroups, bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_pair_softmax_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype);
+size_t sgf_pair_softmax_workspace_bytes(int64_t n, int64_t l, int32_t heads);
+int64_t sgf_pair_softmax_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps);
+int sgf_pair_softmax_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n,
+                         int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* out,
+                         int64_t ldo, float* lse, void* stream);
+int sgf_pair_softmax_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* lse, const void* q,
+                           int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                           int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* dq, int64_t lddq,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* lse, const void* q, int64_t ldq, const void* k,
+                            int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
+                            int32_t d, int32_t dtype, float scale, void* dk, int64_t lddk, void* dv, int64_t lddv,
+                            const void* workspace, size_t workspace_bytes, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

@@ -1,0 +1,248 @@
+#!/usr/bin/env python
+"""The exact softmax attention: the tiled kernels of csrc/pair_attn.hip block N8 (pair_attn.softmax_attention) against (a) the
+dense path (ours_soft._dense_attention: two einsums and [n, l, H] scores and weights) and (b) the sigmoid kernels of block N7
+(pair_attn.sigmoid_attention) at the same shape, on one MI355X, in ONE process with the three paths interleaved.  Sizes
+n = l in {5 000, 10 000, 20 000, 40 000}, D in {32, 64, 128}, H in {1, 2, 4}, bf16 and fp32 storage, scale = 1.  Per cell, HIP
+events around (a) the forward and (b) forward + backward, median (min .. max) of 5 repetitions after 2 warm-ups, the order of
+the paths rotating; torch.cuda.max_memory_allocated of the softmax kernels and of the dense path over the operands; the
+kernels' rate as 4 n l H D / t (forward) and 14 n l H D / t (backward = (b) - (a)).  A dense leg that runs out of memory is
+written as OOM and not retried.  The allocator cache is emptied between cells, not between repetitions, so the dense path's
+timings exclude the device allocation of its score tensors after the warm-ups.
+Writes a markdown report (the worst error ratios of tests/test_gpu_pair_softmax.py are appended from --ratios, the
+`PAIR_RATIO` lines of a `pytest -s` run of that file) and prints one JSON line (also kept, cell by cell, in --json); --cells
+FILE rewrites the report from such a line.  One process, no retries: run it under one time limit,
+    timeout -k 10 1100 python scripts/pair_softmax_probe.py [--out profiles/pair_softmax_probe.md] [--ratios LOG]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sgformer_amd import pair_attn  # noqa: E402
+from sgformer_amd.ours_soft import _dense_attention  # noqa: E402
+
+SIZES = (5000, 10000, 20000, 40000)
+HEADS = (1, 2, 4)
+WIDTHS = (32, 64, 128)
+WARM, REPS = 2, 5
+PATHS = ("softmax", "dense", "sigmoid")
+
+
+def fmt(ms):
+    return "OOM" if ms is None else f"{statistics.median(ms):.3f} ({min(ms):.3f} .. {max(ms):.3f})"
+
+
+def run(path, q, k, v, g, backward):
+    """one timed call: milliseconds between two events on the current stream"""
+    ops = [t.detach().requires_grad_(backward) for t in (q, k, v)]
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    if path == "softmax":
+        out = pair_attn.softmax_attention(*ops)
+    elif path == "sigmoid":
+        out = pair_attn.sigmoid_attention(*ops)
+    else:
+        out = _dense_attention(*ops, False, "keys")[0]
+    if backward:
+        out.backward(g)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def leg(path, q, k, v, g, backward):
+    """(milliseconds or None on OOM, peak bytes over the operands)"""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    try:
+        t = run(path, q, k, v, g, backward)
+    except torch.OutOfMemoryError:
+        torch.cuda.empty_cache()
+        return None, None
+    return t, torch.cuda.max_memory_allocated() - base
+
+
+def cell(n, h, d, dtype, dev):
+    gen = torch.Generator().manual_seed(n + h + d)
+    q, k = ((2.0 / d ** 0.5) * torch.randn(n, h, d, generator=gen) for _ in range(2))
+    v, g = (torch.randn(n, h, d, generator=gen) for _ in range(2))
+    q, k, v, g = (t.to(dev, dtype) for t in (q, k, v, g))
+    res = {}
+    for backward in (False, True):
+        torch.cuda.empty_cache()
+        times = {p: [] for p in PATHS}
+        peak = {p: 0 for p in PATHS}
+        for rep in range(WARM + REPS):
+            for i in range(len(PATHS)):
+                path = PATHS[(i + rep) % len(PATHS)]
+                if times[path] is None:
+                    continue
+                t, mem = leg(path, q, k, v, g, backward)
+                if t is None:
+                    times[path] = None               # OOM: written as such, not retried
+                    continue
+                peak[path] = max(peak[path], mem)
+                if rep >= WARM:
+                    times[path].append(t)
+        res["fwdbwd" if backward else "fwd"] = (times, peak)
+    return res
+
+
+def ratios(path):
+    worst = {}
+    if path and os.path.exists(path):
+        for line in open(path):
+            p = line[max(line.find("PAIR_RATIO "), 0):].split()       # (pytest -q -s puts its progress dots in front)
+            if len(p) == 3 and p[0] == "PAIR_RATIO":
+                name = p[1]
+                kind = name.split("[")[0] + "/" + ("bf16" if "bfloat16" in name else "fp32") + "/" + name.rsplit(".", 1)[-1]
+                if float(p[2]) > worst.get(kind, (-1.0, ""))[0]:
+                    worst[kind] = (float(p[2]), name)
+    return worst
+
+
+def resources(path):
+    """[(kernel, VGPRs, AGPRs, spilled VGPRs, scratch bytes per lane, waves per SIMD, LDS bytes)] of the k_ps_* kernels from the
+    compiler's remarks (hipcc ... -Rpass-analysis=kernel-resource-usage -c sgformer_amd/csrc/pair_attn.hip 2> FILE)"""
+    import re
+    rows = []
+    if path and os.path.exists(path):
+        for block in re.split(r"remark: [^\n]*Function Name: ", open(path).read())[1:]:
+            m = re.match(r"\S*?(k_ps_\w+?)I([ft])Li(\d+)E", block)
+            if m:
+                get = lambda key: int(re.search(key + r": (\d+)", block).group(1))      # noqa: E731
+                rows.append((f"{m.group(1)}<{'fp32' if m.group(2) == 'f' else 'bf16'}, {m.group(3)}>", get("VGPRs"), get("AGPRs"),
+                             get("VGPRs Spill"), get(r"ScratchSize \[bytes/lane\]"), get(r"Occupancy \[waves/SIMD\]"),
+                             get(r"LDS Size \[bytes/block\]")))
+    return rows
+
+
+def ahead(c):
+    """the kernels' slowest repetition beats the dense path's fastest one (or the dense path is OOM), both timings"""
+    return all(c[d] is None or max(c[k]) < min(c[d]) for k, d in (("fwd_softmax", "fwd_dense"), ("fwdbwd_softmax", "fwdbwd_dense")))
+
+
+def threshold(cells):
+    """smallest probed n l H such that every cell of that size or larger is ahead; 0: every cell; None: not even the largest"""
+    sizes = sorted({c["pairs"] for c in cells})
+    behind = sorted({c["pairs"] for c in cells if not ahead(c)})
+    if not behind:
+        return 0, behind
+    above = [s for s in sizes if s > behind[-1]]
+    return (above[0] if above else None), behind
+
+
+def report(cells, worst, out, regs=()):
+    mb = lambda x: "-" if not x else f"{x / 2 ** 20:.0f}"     # noqa: E731
+    med = statistics.median
+    with open(out, "w") as f:
+        f.write("# Softmax attention: tiled kernels against the dense path and the sigmoid kernels (scripts/pair_softmax_probe.py)\n\n")
+        f.write(f"One MI355X, one process, the three paths interleaved; HIP events; milliseconds as median (min .. max) of {REPS} "
+                f"repetitions after {WARM} warm-ups.  n = l, scale = 1.  Peak = torch.cuda.max_memory_allocated over the operands "
+                "in MiB (forward + backward).  TF/s: the softmax kernels' 4 n l H D / t forward and 14 n l H D / "
+                "(t_fwdbwd - t_fwd) backward.  x sigmoid: the softmax kernels' median over the sigmoid kernels' median at the "
+                "same shape (forward; forward + backward).  The dense path is ours_soft._dense_attention.\n\n")
+        f.write("| dtype | n | H | D | fwd softmax | fwd dense | fwd sigmoid | fwd+bwd softmax | fwd+bwd dense | fwd+bwd sigmoid | "
+                "peak softmax | peak dense | TF/s fwd | TF/s bwd | x sigmoid | ahead |\n" + "|---" * 16 + "|\n")
+        for c in cells:
+            xs = f"{med(c['fwd_softmax']) / med(c['fwd_sigmoid']):.2f}; {med(c['fwdbwd_softmax']) / med(c['fwdbwd_sigmoid']):.2f}"
+            f.write(f"| {c['dtype']} | {c['n']} | {c['heads']} | {c['d']} | {fmt(c['fwd_softmax'])} | {fmt(c['fwd_dense'])} | "
+                    f"{fmt(c['fwd_sigmoid'])} | {fmt(c['fwdbwd_softmax'])} | {fmt(c['fwdbwd_dense'])} | {fmt(c['fwdbwd_sigmoid'])} | "
+                    f"{mb(c['peak_softmax'])} | {mb(c['peak_dense']) if c['fwdbwd_dense'] else 'OOM'} | {c['tflops_fwd']:.1f} | "
+                    f"{c['tflops_bwd']:.1f} | {xs} | {'yes' if ahead(c) else 'NO'} |\n")
+        f.write("\n## SOFTMAX_MIN_PAIRS\n\nRule, per storage dtype (the rule of PAIR_MIN_PAIRS): a cell is ahead when, for the forward "
+                "and for forward + backward, the kernels' slowest repetition is faster than the dense path's fastest one (or the "
+                "dense path is OOM).  The threshold is the smallest probed n l H such that every cell of that size or larger, at "
+                "every probed head count and width, is ahead; 0 when every cell is.\n\n")
+        res = {}
+        for dt in sorted({c["dtype"] for c in cells}):
+            t, behind = threshold([c for c in cells if c["dtype"] == dt])
+            res[dt] = t
+            f.write(f"* {dt}: cells NOT ahead at n l H = {behind if behind else 'none'}; threshold = {t}.\n")
+        f.write("\n`pair_attn.SOFTMAX_MIN_PAIRS` (fp32 storage) and `pair_attn.SOFTMAX_MIN_PAIRS_BF16` hold these two numbers.\n\n")
+        f.write("## Against the sigmoid kernels\n\n")
+        for dt in sorted({c["dtype"] for c in cells}):
+            rs = [(med(c["fwd_softmax"]) / med(c["fwd_sigmoid"]), c) for c in cells if c["dtype"] == dt]
+            lo, hi = min(rs, key=lambda r: r[0]), max(rs, key=lambda r: r[0])
+            f.write(f"* {dt}, forward: {lo[0]:.2f} x (n = {lo[1]['n']}, H = {lo[1]['heads']}, D = {lo[1]['d']}) to {hi[0]:.2f} x "
+                    f"(n = {hi[1]['n']}, H = {hi[1]['heads']}, D = {hi[1]['d']}); median {med([r[0] for r in rs]):.2f} x.\n")
+        slow = [(r, c) for dt in ("bfloat16", "float32") for r, c in
+                ((med(c["fwd_softmax"]) / med(c["fwd_sigmoid"]), c) for c in cells if c["dtype"] == dt) if r > 1.5]
+        if slow:
+            f.write("\nForward above 1.5 x the sigmoid forward: " + ", ".join(
+                f"{c['dtype']} n = {c['n']} H = {c['heads']} D = {c['d']} ({r:.2f} x)" for r, c in slow) + ".\n")
+        f.write("\nWhat the softmax adds per score is one exchange of the stage maximum between the lane halves, one multiply of the "
+                "accumulators per stage and one `v_exp` where the sigmoid has `v_exp` + `v_rcp`: level with the sigmoid kernels at "
+                "D = 32 / 64.  At D = 128 the forward is compiled for two waves per SIMD (`__launch_bounds__(256, 2)`): left to its "
+                "default the compiler took 261 (bf16) / 283 (fp32) registers, one wave per SIMD where the sigmoid forward has two, "
+                "and an earlier run of this probe measured that forward at 1.4 - 2.0 x the sigmoid forward in bf16 from 10 000 "
+                "nodes x 4 heads upward (1.2 - 1.5 x in fp32); the time went to occupancy, not to the exchange or the rescale.\n")
+        if regs:
+            f.write("\n## Registers (the compiler's resource summary, gfx950)\n\n| kernel | VGPRs | AGPRs | spilled | scratch B/lane | "
+                    "waves/SIMD | LDS B |\n|---|---|---|---|---|---|---|\n")
+            for r in regs:
+                f.write("| " + " | ".join(str(x) for x in r) + " |\n")
+            f.write("\n" + ("No instantiation spills.\n" if not any(r[3] or r[4] for r in regs) else "SPILLS: see the table.\n"))
+        if worst:
+            f.write("\n## Worst error / bar of tests/test_gpu_pair_softmax.py\n\n| check | worst ratio | case |\n|---|---|---|\n")
+            for kind in sorted(worst):
+                f.write(f"| {kind} | {worst[kind][0]:.4f} | {worst[kind][1]} |\n")
+            over = [k for k in worst if worst[k][0] > 0.5 and not k.startswith(("fixture_shipped", "large"))]
+            f.write("\n" + (f"Above 0.5 of the bar: {', '.join(sorted(over))}.\n" if over else "No asserted ratio exceeds 0.5.\n"))
+            f.write("\nmoving.rising32/fp32/out is measured against a bar of its own, 2 x the measured 1.9791e-4 max|v| (the "
+                    "project's rule for a bound the formats set): with the maximum rising by 40 at every 32-row tile the scores "
+                    "reach 1280, where the 32 accumulation steps of an fp32 score leave about 2e-4 of absolute error in z, the "
+                    "relative error of P in any fp32 evaluation; against the common 1e-4 max|v| bar the ratio is 1.98 (0.82 with "
+                    "the rise every 64 rows, scores to 640).  The `large` rows (|z| to 3000) are printed, not asserted: that test "
+                    "asserts finite outputs.  The fixture rows are the module with the softmax over the keys; as constructed it "
+                    "computes the reference as shipped, in plain PyTorch.\n")
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pair_softmax_probe.md"))
+    ap.add_argument("--ratios", default=None, help="output of `pytest -s tests/test_gpu_pair_softmax.py` (PAIR_RATIO lines)")
+    ap.add_argument("--cells", default=None, help="the JSON line of an earlier run: rewrite the report, measure nothing")
+    ap.add_argument("--resources", default=None, help="the compiler's kernel-resource-usage remarks for csrc/pair_attn.hip")
+    ap.add_argument("--json", default=None, help="keep the cells measured so far in this file (rewritten after every cell)")
+    ap.add_argument("--sizes", default=",".join(str(s) for s in SIZES))
+    ap.add_argument("--heads", default=",".join(str(s) for s in HEADS))
+    ap.add_argument("--widths", default=",".join(str(s) for s in WIDTHS))
+    args = ap.parse_args()
+    if args.cells:
+        cells = json.loads([ln for ln in open(args.cells) if ln.startswith("{")][-1])["cells"]
+    else:
+        dev = torch.device("cuda:0")
+        os.environ["SGF_PAIR_ATTN"] = os.environ["SGF_PAIR_SOFTMAX"] = "1"
+        cells = []
+        for dtype in (torch.bfloat16, torch.float32):
+            for n in (int(s) for s in args.sizes.split(",")):
+                for h in (int(s) for s in args.heads.split(",")):
+                    for d in (int(s) for s in args.widths.split(",")):
+                        r = cell(n, h, d, dtype, dev)
+                        (tf, pf), (tb, pb) = r["fwd"], r["fwdbwd"]
+                        kf, kb = statistics.median(tf["softmax"]), statistics.median(tb["softmax"])
+                        pairs = n * n * h
+                        c = dict(dtype=str(dtype)[6:], n=n, heads=h, d=d, pairs=pairs, peak_softmax=pb["softmax"],
+                                 peak_dense=pb["dense"], tflops_fwd=4 * pairs * d / (kf * 1e-3) / 1e12,
+                                 tflops_bwd=14 * pairs * d / (max(kb - kf, 1e-6) * 1e-3) / 1e12)
+                        for p in PATHS:
+                            c["fwd_" + p], c["fwdbwd_" + p] = tf[p], tb[p]
+                        cells.append(c)
+                        print(f"{c['dtype']} n={n} H={h} D={d}: fwd {fmt(tf['softmax'])} / {fmt(tf['dense'])} / {fmt(tf['sigmoid'])}, "
+                              f"fwd+bwd {fmt(tb['softmax'])} / {fmt(tb['dense'])} / {fmt(tb['sigmoid'])}", flush=True)
+                        if args.json:
+                            with open(args.json, "w") as f:
+                                f.write(json.dumps(dict(probe="pair_softmax", cells=cells)) + "\n")
+    res = report(cells, ratios(args.ratios), args.out, resources(args.resources))
+    print(json.dumps(dict(probe="pair_softmax", thresholds=res, cells=cells)))
+
+
+if __name__ == "__main__":
+    main()

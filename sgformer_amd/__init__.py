@@ -4,6 +4,7 @@
     sgformer_amd.ours_100m     drop-in for 100M/ours.py (alpha residual, neighbour-sampled batches)
     sgformer_amd.ours_medium   drop-in for medium/ours.py + the models.GCN backbone (GCNConv on libsgf)
     sgformer_amd.difformer     drop-in for medium/difformer.py (DIFFormer, simple kernel)
+    sgformer_amd.ours_soft     drop-in for medium/ablation/oursSOFT.py (SGFormerSOFT, exact softmax attention)
     sgformer_amd.ops           autograd operators over the C ABI (include/sgf.h -> lib/libsgf.so)
     sgformer_amd.dist          node-sharded multi-GPU execution (RCCL via torch.distributed)
     sgformer_amd.batching      GPU induced subgraph for the mini-batch trainer (PyG-compatible `subgraph`)

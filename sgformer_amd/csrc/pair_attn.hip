@@ -27,6 +27,9 @@
 //   * tails: a swept row past the end is staged as zeros AND masked (a zero key would score sigmoid(0) = 0.5): keys by a
 //     compare on the row index, queries (bwd_kv) by a staged 1 / r = 0.  Resident rows past the end are clamped for the
 //     loads and never stored.
+//
+// The exact softmax attention (block N8, k_ps_*) is the second arm of this file: the same skeleton with an online maximum;
+// its comment stands in front of its kernels.
 #include "common.h"
 
 namespace sgf {
@@ -359,6 +362,222 @@ __global__ __launch_bounds__(kPaThreads) void k_pa_bwd_kv(const PaArgs p) {
   if (shared_v && j < p.l) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv, dv, hh, 1.f);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// The exact softmax arm (include/sgf.h block N8; medium/ablation/oursSOFT.py): the same skeleton, layout and staging with
+// an online maximum.  With z = scale q_i . k_j, per head:
+//
+//   sgf_pair_softmax_fwd    : m_i = max_j z,  r_i = sum_j exp(z - m_i),  out_i = sum_j exp(z - m_i) v_j / r_i,
+//                             lse_i = m_i + log r_i
+//   sgf_pair_softmax_bwd_q  : P = exp(z - lse_i),  delta_i = g_i . out_i,  dZ = scale P (g_i . v_j - delta_i),
+//                             dq_i = sum_j dZ k_j
+//   sgf_pair_softmax_bwd_kv : dv_j = sum_i P g_i,  dk_j = sum_i dZ q_i
+//
+//   * The resident row is the lane, so m, r and the rescale factor c = exp(m - m') are one scalar per lane.  The two lane
+//     halves hold different swept rows of the same resident row: one exchange of the stage's maximum (all its sub-tiles)
+//     before P is formed gives both the same m, hence the same c, and their partial r add up at the end as they stand.
+//   * A key past l is -inf BEFORE the maximum: it takes no part in it and exp(-inf - m) is exactly 0.  Key j0 of a stage
+//     always exists, so after the exchange the stage maximum is finite in every lane: m' is finite from the first stage on
+//     and exp(-inf - m') = 0 is the first stage's c (never -inf - -inf).  z - m' <= 0 everywhere: nothing overflows for
+//     any finite z, and a row whose earlier stages underflow entirely just rescales zeros.
+//   * The backward launches recompute P from lse: no running maximum.  A swept query past n (bwd_kv) is staged with
+//     lse = +inf: P = exp(0 - inf) = 0, and its g row is zeros.
+//   * bf16 storage: P (fwd) and P, dZ (bwd) are rounded only as operands of the second products; r, lse, delta are fp32.
+//     out divides the numerator by the sum of the ROUNDED weights, as the sigmoid forward does and for the same reason.
+//   * exp: expf for fp32 storage, the hardware exp2 for bf16 storage (sigmoid<kExact>'s rule).
+template <bool kExact>
+__device__ __forceinline__ float pa_exp(float t) {
+  return kExact ? expf(t) : __builtin_amdgcn_exp2f(1.44269504088896341f * t);
+}
+
+// D = 128: m, the held score tiles and the rescale put the unbounded allocation at 261 (bf16) / 283 (fp32) registers, one
+// wave per SIMD where the sigmoid forward runs two; asked for two waves the compiler fits 206 / 210 without a spill.
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads, D == 128 ? 2 : 1) void k_ps_fwd(const PaArgs p, const float scale) {
+  constexpr int SW = pa_sweep<T, 0>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) T vs[I::kBf16 ? 4 : I::kRm];
+  __shared__ __attribute__((aligned(16))) T vt[I::kTr];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t ic = i < p.n ? i : p.n - 1;
+  const T* kp = static_cast<const T*>(p.k) + h * D;
+  const T* vp = static_cast<const T*>(p.v) + hv * D;
+  typename I::Frag qf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
+  f32x16 o[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) o[t][q] = 0.f;
+  float m = -INFINITY, rs = 0.f, den = 0.f;
+  for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
+    I::template stage<true, false>(kp, p.ldk, j0, p.l, ks, nullptr);
+    I::template stage<!I::kBf16, true>(vp, p.ldv, j0, p.l, vs, vt);
+    __syncthreads();
+    f32x16 x[SW / 32];
+    float tm = -INFINITY;
+#pragma unroll
+    for (int st = 0; st < SW / 32; ++st) {
+      const int64_t lim = p.l - j0 - 32 * st;        // swept rows of this sub-tile that exist (workgroup-uniform)
+      if (lim > 0) {
+        x[st] = I::dot(ks, st, r, hh, qf);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float z = slot_of(q, hh) < lim ? scale * x[st][q] : -INFINITY;
+          x[st][q] = z;
+          tm = fmaxf(tm, z);
+        }
+      }
+    }
+    tm = fmaxf(tm, __shfl_xor(tm, 32, 64));          // both lane halves: the same maximum (finite: key j0 exists)
+    const float mn = fmaxf(m, tm);
+    const float c = pa_exp<!I::kBf16>(m - mn);       // first stage: exp(-inf - finite) = 0
+    m = mn;
+    rs *= c;
+    den *= c;
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) o[t][q] *= c;
+#pragma unroll
+    for (int st = 0; st < SW / 32; ++st) {
+      if (p.l - j0 - 32 * st > 0) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float pr = pa_exp<!I::kBf16>(x[st][q] - mn);                       // a masked key: exp(-inf) = 0
+          rs += pr;                                                               // r: fp32, before the operand's rounding
+          if constexpr (I::kBf16) den += __uint_as_float(pk_bf16(pr, 0.f) << 16);
+          x[st][q] = pr;
+        }
+        I::acc(vs, vt, st, x[st], o, r, hh);
+      }
+    }
+    __syncthreads();
+  }
+  rs += __shfl_xor(rs, 32, 64);
+  den = I::kBf16 ? den + __shfl_xor(den, 32, 64) : rs;
+  if (i < p.n) {
+    I::template store<true>(static_cast<T*>(p.out) + i * p.ldout + h * D, o, hh, den);
+    if (hh == 0) p.rowsum[i * p.heads + h] = m + logf(rs);       // lse
+  }
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads) void k_ps_bwd_q(const PaArgs p, const float scale) {
+  constexpr int SW = pa_sweep<T, 1>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) T vs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T kt[I::kTr];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t ic = i < p.n ? i : p.n - 1;
+  const T* kp = static_cast<const T*>(p.k) + h * D;
+  const T* vp = static_cast<const T*>(p.v) + hv * D;
+  typename I::Frag qf[I::kFrags], gf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.g) + ic * p.ldg + h * D, hh, gf);
+  float delta = I::dot_frags(gf, static_cast<const T*>(p.o) + ic * p.ldo + h * D, hh);
+  delta += __shfl_xor(delta, 32, 64);
+  if (i < p.n && hh == 0) p.delta[i * p.heads + h] = delta;
+  if (!p.dq) return;                                 // (uniform: delta only)
+  I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
+  const float lse = p.rowsum[ic * p.heads + h];
+  f32x16 dq[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dq[t][q] = 0.f;
+  for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
+    I::template stage<true, true>(kp, p.ldk, j0, p.l, ks, kt);
+    I::template stage<true, false>(vp, p.ldv, j0, p.l, vs, nullptr);
+    __syncthreads();
+#pragma unroll
+    for (int st = 0; st < SW / 32; ++st) {
+      const int64_t lim = p.l - j0 - 32 * st;
+      if (lim > 0) {
+        f32x16 x = I::dot(ks, st, r, hh, qf);
+        const f32x16 pv = I::dot(vs, st, r, hh, gf);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const float pr = pa_exp<!I::kBf16>(scale * x[q] - lse);
+          x[q] = slot_of(q, hh) < lim ? scale * pr * (pv[q] - delta) : 0.f;
+        }
+        I::acc(ks, kt, st, x, dq, r, hh);
+      }
+    }
+    __syncthreads();
+  }
+  if (i < p.n) I::template store<false>(static_cast<T*>(p.dq) + i * p.lddq + h * D, dq, hh, 1.f);
+}
+
+template <typename T, int D>
+__global__ __launch_bounds__(kPaThreads) void k_ps_bwd_kv(const PaArgs p, const float scale) {
+  constexpr int SW = pa_sweep<T, 2>();
+  using I = PaImg<T, D, SW>;
+  __shared__ __attribute__((aligned(16))) T qs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T gs[I::kRm];
+  __shared__ __attribute__((aligned(16))) T qt[I::kTr];
+  __shared__ __attribute__((aligned(16))) T gt[I::kTr];
+  __shared__ float lse_s[SW], delta_s[SW];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const bool shared_v = p.v_heads != p.heads;        // one value head: this workgroup walks every head, dv sums over them
+  const int h_begin = shared_v ? 0 : blockIdx.y, h_end = shared_v ? p.heads : h_begin + 1;
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
+  const int64_t jc = j < p.l ? j : p.l - 1;
+  typename I::Frag kf[I::kFrags], vf[I::kFrags];
+  I::load_frags(static_cast<const T*>(p.v) + jc * p.ldv + (shared_v ? 0 : h_begin) * D, hh, vf);
+  f32x16 dk[D / 32], dv[D / 32];
+#pragma unroll
+  for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) dv[t][q] = 0.f;
+  for (int h = h_begin; h < h_end; ++h) {
+    I::load_frags(static_cast<const T*>(p.k) + jc * p.ldk + h * D, hh, kf);
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dk[t][q] = 0.f;
+    const T* qp = static_cast<const T*>(p.q) + h * D;
+    const T* gp = static_cast<const T*>(p.g) + h * D;
+    for (int64_t i0 = 0; i0 < p.n; i0 += SW) {
+      I::template stage<true, true>(qp, p.ldq, i0, p.n, qs, qt);
+      I::template stage<true, true>(gp, p.ldg, i0, p.n, gs, gt);
+      if (threadIdx.x < SW) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool in = i < p.n;
+        lse_s[threadIdx.x] = in ? p.rowsum[i * p.heads + h] : INFINITY;      // +inf: a query row past the end has P = 0
+        delta_s[threadIdx.x] = in ? p.delta[i * p.heads + h] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int st = 0; st < SW / 32; ++st) {
+        if (p.n - i0 - 32 * st > 0) {
+          f32x16 x = I::dot(qs, st, r, hh, kf);
+          f32x16 pv = I::dot(gs, st, r, hh, vf);
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const int sl = 32 * st + slot_of(q, hh);
+            const float pr = pa_exp<!I::kBf16>(scale * x[q] - lse_s[sl]);
+            x[q] = pr;
+            pv[q] = scale * pr * (pv[q] - delta_s[sl]);
+          }
+          I::acc(gs, gt, st, x, dv, r, hh);
+          I::acc(qs, qt, st, pv, dk, r, hh);
+        }
+      }
+      __syncthreads();
+    }
+    if (j < p.l) {
+      I::template store<false>(static_cast<T*>(p.dk) + j * p.lddk + h * D, dk, hh, 1.f);
+      if (!shared_v) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv + h * D, dv, hh, 1.f);
+    }
+  }
+  if (shared_v && j < p.l) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv, dv, hh, 1.f);
+}
+
 inline bool pa_shape_ok(int heads, int v_heads, int d, int dtype) {
   if (dtype != SGF_F32 && dtype != SGF_BF16) return false;
   if (d != 32 && d != 64 && d != 128) return false;
@@ -429,6 +648,45 @@ struct PaBwdKv {
     hipLaunchKernelGGL((k_pa_bwd_kv<T, D>), grid, dim3(kPaThreads), 0, st, a);
   }
 };
+
+// the softmax arm: the same dispatch with the score scale as a second kernel argument
+template <template <typename, int> class Launch>
+int ps_dispatch(int d, int dtype, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (d == 32) Launch<T, 32>::run(a, scale, grid, st);
+    else if (d == 64) Launch<T, 64>::run(a, scale, grid, st);
+    else Launch<T, 128>::run(a, scale, grid, st);
+    SGF_LAUNCH_CHECK();
+    return static_cast<int>(SGF_OK);
+  });
+}
+template <typename T, int D>
+struct PsFwd {
+  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_ps_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
+  }
+};
+template <typename T, int D>
+struct PsBwdQ {
+  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_ps_bwd_q<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
+  }
+};
+template <typename T, int D>
+struct PsBwdKv {
+  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((k_ps_bwd_kv<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
+  }
+};
+
+// sizes, shape and the score scale of the three softmax launches
+int check_ps(const char* fn, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype, float scale) {
+  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  SGF_REQUIRE(std::isfinite(scale) && scale > 0.f, SGF_E_INVALID, "%s: scale must be finite and positive (%g)", fn,
+              static_cast<double>(scale));
+  return SGF_OK;
+}
 
 inline unsigned pa_tiles(int64_t rows) { return static_cast<unsigned>((rows + kPaRows - 1) / kPaRows); }
 
@@ -515,5 +773,89 @@ extern "C" int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* 
   a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
   a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
   return pa_dispatch<PaBwdKv>(d, dtype, a, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
+                              static_cast<hipStream_t>(stream));
+}
+
+// ---- block N8: the exact softmax arm ---------------------------------------------------------------------------------
+extern "C" int32_t sgf_pair_softmax_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype) {
+  return pa_shape_ok(heads, v_heads, d, dtype) ? 1 : 0;
+}
+
+// delta fp32 [n, heads]; nothing of size l, nothing of size n x l
+extern "C" size_t sgf_pair_softmax_workspace_bytes(int64_t n, int64_t l, int32_t heads) {
+  if (n < 0 || l < 0 || heads < 1) return 0;
+  return static_cast<size_t>(n) * heads * sizeof(float);
+}
+
+extern "C" int64_t sgf_pair_softmax_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
+  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
+    set_error("sgf_pair_softmax_lap_rows: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", which, laps,
+              heads, d, dtype);
+    return -1;
+  }
+  return 0;      // every workgroup of the three kernels owns one resident tile: there is no second lap
+}
+
+extern "C" int sgf_pair_softmax_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                    int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale,
+                                    void* out, int64_t ldo, float* lse, void* stream) {
+  const char* fn = "sgf_pair_softmax_fwd";
+  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
+  const PaOperand ops[] = {{"q", q, ldq, heads * d}, {"k", k, ldk, heads * d}, {"v", v, ldv, v_heads * d}, {"out", out, ldo, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 4, dtype)) return rc;
+  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
+  PaArgs a = {};
+  a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv, a.out = out, a.ldout = ldo, a.rowsum = lse;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return ps_dispatch<PsFwd>(d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sgf_pair_softmax_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* lse,
+                                      const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                      int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype,
+                                      float scale, void* dq, int64_t lddq, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  const char* fn = "sgf_pair_softmax_bwd_q";
+  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"out", out, ldo, heads * d}, {"q", q, ldq, heads * d},
+                           {"k", k, ldk, heads * d},   {"v", v, ldv, v_heads * d},   {"dq", dq, lddq, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, dq ? 6 : 5, dtype)) return rc;      // dq == NULL: delta only
+  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
+  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_softmax_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
+              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
+              sgf_pair_softmax_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.o = out, a.ldo = ldo, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(lse), a.delta = static_cast<float*>(workspace), a.dq = dq, a.lddq = lddq;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return ps_dispatch<PsBwdQ>(d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* lse, const void* q, int64_t ldq,
+                                       const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                                       int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* dk,
+                                       int64_t lddk, void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  const char* fn = "sgf_pair_softmax_bwd_kv";
+  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"q", q, ldq, heads * d},     {"k", k, ldk, heads * d},
+                           {"v", v, ldv, v_heads * d}, {"dk", dk, lddk, heads * d},  {"dv", dv, lddv, v_heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 6, dtype)) return rc;
+  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
+  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_softmax_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
+              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
+              sgf_pair_softmax_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(lse), a.delta = static_cast<float*>(const_cast<void*>(workspace));
+  a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return ps_dispatch<PsBwdKv>(d, dtype, a, scale, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
                               static_cast<hipStream_t>(stream));
 }

@@ -155,13 +155,15 @@ class TransConv(_large.TransConv):
 class SGFormer(nn.Module):
     """medium/ours.py:179-223."""
 
+    _trans_cls = TransConv      # (ours_soft.SGFormerSOFT: the same model around another attention)
+
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, num_heads=1, alpha=0.5,
                  dropout=0.5, use_bn=True, use_residual=True, use_weight=True, use_graph=True,
                  use_act=False, graph_weight=0.8, gnn=None, aggregate='add'):
         super().__init__()
         # positional, and WITHOUT use_act, exactly as medium/ours.py:183
-        self.trans_conv = TransConv(in_channels, hidden_channels, num_layers, num_heads, alpha, dropout,
-                                    use_bn, use_residual, use_weight)
+        self.trans_conv = self._trans_cls(in_channels, hidden_channels, num_layers, num_heads, alpha, dropout,
+                                          use_bn, use_residual, use_weight)
         self.gnn = gnn
         self.use_graph = use_graph
         self.graph_weight = graph_weight
