@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 667 /* 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 668 /* 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -1225,6 +1225,28 @@ int sgf_sum_n(const void* const* xs_host, const int64_t* lds_host, int32_t k, in
 size_t sgf_colsum_workspace_bytes(int64_t n, int32_t d);
 int sgf_colsum(const void* x, int64_t ldx, int64_t n, int32_t d, int32_t dtype, float* out,
                void* workspace, size_t workspace_bytes, void* stream);
+
+/* Geometry of the persistent element-wise, normalisation and loss kernels of csrc/fused.hip (host query, no GPU needed; the
+ * counterpart of sgf_row_lap_rows).  Their grids are capped (8 workgroups of 256 threads per CU) and every workgroup walks
+ * its rows in a loop; the result is the number of rows ONE loop iteration of the capped grid covers for the kernel the
+ * entry would launch, so a launch over more than k times that many rows gives every workgroup more than k iterations.
+ * kind:
+ *    0 sgf_ln_fwd                           5 sgf_sum_n                          10 sgf_colstats / sgf_bn_bwd_stats / _stats2
+ *    1 sgf_ln_bwd                           6 sgf_dropout / sgf_dropout_dev      11 sgf_colsum
+ *    2 sgf_bn_apply                         7 sgf_gather_rows                    12 sgf_nll_fwd (d = c)
+ *    3 sgf_bn_bwd_apply                     8 sgf_pad_rows (d = d_pad)
+ *    4 sgf_axpby                            9 sgf_nll_bwd (d = c; TRAINING rows)
+ * wide = 1 asks for the kernel that moves bf16 rows as 16 bytes per lane (kinds 0, 1: d in {64, 128, 256, 512}; 2, 3, 5, 10:
+ * d % 8 == 0), which the entry launches when every row is 16-byte aligned (kinds 1, 2, 3, 10 also: unless SGF_EW8=0);
+ * wide = 0 for the fp32 and the 8-byte bf16 kernels.
+ *   - kinds 4 - 8 are flat: a thread takes one chunk of a row (4 columns; 8 when wide; kind 8 and kind 7 with d % 4 != 0: one
+ *     element) and the grid strides over all chunks, so an iteration ends INSIDE a row when the chunks per row do not divide
+ *     256 * grid; the result is the whole rows of one iteration, rounded down.
+ *   - kinds 10 - 12 are blocked (workgroup b takes the rows [b r, (b + 1) r), r = ceil(n / grid)): the result is the row
+ *     count at which the grid stops growing; beyond it r grows, and trailing workgroups may have no rows at all.
+ * -1 for an unknown kind, a width or dtype the entry rejects (kinds 0 - 6, 10: d % 4 == 0, d <= 1024; 11: d <= 256; 7, 8: d <= 2^20), or a
+ * wide form that does not exist.  The entries size their grids with the functions this reads. */
+int64_t sgf_ew_lap_rows(int32_t kind, int32_t d, int32_t dtype, int32_t wide);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY.md §8b / §8e — the collectives of the node-sharded run (csrc/comm.hip): thin wrappers over RCCL, which is loaded

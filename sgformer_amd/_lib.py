@@ -102,6 +102,7 @@ SIGNATURES = {
     "sgf_attn_max_blocks": (c_int32, []),
     "sgf_attn_tile_rows": (c_int32, [c_int32, c_int32, c_int32]),
     "sgf_row_lap_rows": (c_int32, [c_int32, c_int32, c_int32]),
+    "sgf_ew_lap_rows": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "sgf_attn_fwd_reduce": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32,
                                       c_int32, c_int32, _P, _P, c_size_t, _P]),
     "sgf_attn_fwd_apply": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_double, c_int32, c_int32,

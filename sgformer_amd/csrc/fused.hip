@@ -1321,9 +1321,23 @@ inline int ew_grid(int64_t total_vec) { return clamp_grid(ceil_div(total_vec, kT
 
 // blocks for the column-fixed row-walk kernels: enough to fill the chip (8 blocks / CU), never more
 // than one unrolled pass of rows per block
-inline int rowwalk_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, static_cast<int64_t>(kThreads / (d / 4)) * kRowUnroll)); }
+inline int64_t rowwalk_block_rows(int d) { return static_cast<int64_t>(kThreads / (d / 4)) * kRowUnroll; }
+inline int rowwalk_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, rowwalk_block_rows(d))); }
 
-inline int stat_blocks(int64_t n) { return clamp_grid(ceil_div(n, 64), kMaxStatBlocks); }  // >= 64 rows per block
+constexpr int kStatBlockRows = 64;                     // >= 64 rows per block
+inline int stat_blocks(int64_t n) { return clamp_grid(ceil_div(n, kStatBlockRows), kMaxStatBlocks); }
+
+// the generic LayerNorm kernels (k_ln_fwd, k_ln_bwd): one row per group of lanes_per_row(d) lanes in every loop iteration
+inline int64_t ln_block_rows(int d) { return kThreads / lanes_per_row(d); }
+inline int ln_fwd_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, ln_block_rows(d))); }
+inline int ln_bwd_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, ln_block_rows(d)), kMaxStatBlocks); }
+
+// the loss kernels: k_nll_fwd / k_nll_fwd16 are blocked (>= 64 training rows per block), k_nll_bwd16 / k_nll_bwd take 16 / 4
+// training rows per block and loop iteration (one per 16 lanes, one per wave)
+constexpr int kNllBlockRows = 64;
+inline int nll_fwd_blocks(int64_t m) { return clamp_grid(ceil_div(m, kNllBlockRows), kNllMaxBlocks); }
+inline int64_t nll_bwd_block_rows(int c) { return c <= 64 ? 16 : 4; }
+inline int nll_bwd_grid(int64_t m, int c) { return clamp_grid(ceil_div(m, nll_bwd_block_rows(c))); }
 
 int check_ew(const char* fn, int64_t n, int d, int dtype) {
   SGF_REQUIRE(n >= 0 && d >= 1, SGF_E_INVALID, "%s: bad sizes n=%lld d=%d", fn,
@@ -1375,15 +1389,22 @@ inline bool rows16(std::initializer_list<std::pair<const void*, int64_t>> ops) {
     if (o.first && (reinterpret_cast<uintptr_t>(o.first) % 16 != 0 || o.second % 8 != 0)) return false;
   return true;
 }
+inline bool ew8_width(int d) { return d % 8 == 0 && d / 8 <= kThreads; }
 inline bool ew8_rows(int d, std::initializer_list<std::pair<const void*, int64_t>> ops) {
   static EnvInt ew8{"SGF_EW8", 1};
-  return ew8.get() != 0 && d % 8 == 0 && d / 8 <= kThreads && rows16(ops);
+  return ew8.get() != 0 && ew8_width(d) && rows16(ops);
 }
 constexpr int kEw8Unroll = 4;   // rows in flight per lane (2 / 4 / 8 measured 0.77 / 0.71 / 0.70 ms on the 2R:1W apply; 8 loses on the statistics)
-inline int rowwalk8_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, static_cast<int64_t>(kThreads / (d / 8)) * kEw8Unroll)); }
+inline int64_t rowwalk8_block_rows(int d) { return static_cast<int64_t>(kThreads / (d / 8)) * kEw8Unroll; }
+inline int rowwalk8_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, rowwalk8_block_rows(d))); }
 
 // the 16-byte LayerNorm kernels: d in {64, 128, 256, 512}, one lane per 8 columns; f gets the lanes per row as an integral_constant
 inline bool ln8_width(int d) { return d == 64 || d == 128 || d == 256 || d == 512; }
+// kLn8Rows rows in flight per lane (backward: 2 / 4 / 8 measured 1.26 / 1.20 / 1.22 ms)
+constexpr int kLn8Rows = 4;
+inline int64_t ln8_block_rows(int d) { return kThreads / (d / 8) * kLn8Rows; }
+inline int ln8_fwd_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, ln8_block_rows(d))); }
+inline int ln8_bwd_grid(int64_t n, int d) { return clamp_grid(ceil_div(n, ln8_block_rows(d)), kMaxStatBlocks); }
 template <typename F>
 int by_ln8_lanes(int d, F&& f) {
   switch (d / 8) {
@@ -1399,16 +1420,15 @@ int ln_fwd_t(const void* x, int64_t ldx, const void* res, int64_t ldr, float a, 
              const float* gamma, const float* beta, int relu, float eps, int64_t n, int d, void* y,
              int64_t ldy, float* mean, float* rstd, hipStream_t st) {
   if (sizeof(T) == 2 && ln8_width(d) && rows16({{x, ldx}, {y, ldy}, {res, ldr}})) {   // (not under SGF_EW8)
-    constexpr int R = 4;
-    const dim3 grid(clamp_grid(ceil_div(n, kThreads / (d / 8) * R)));
+    const dim3 grid(ln8_fwd_grid(n, d));
     return by_ln8_lanes(d, [&](auto l) {
-      return launch(k_ln_fwd_bf16x8<decltype(l)::value, R>, grid, st, x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, y,
+      return launch(k_ln_fwd_bf16x8<decltype(l)::value, kLn8Rows>, grid, st, x, ldx, res, ldr, a, b, gamma, beta, relu, eps, n, y,
                     ldy, mean, rstd);
     });
   }
   const int lpr = lanes_per_row(d);
   const int nc = (d + 4 * lpr - 1) / (4 * lpr);
-  return launch_ln<LnFwd, T>(lpr, nc, dim3(clamp_grid(ceil_div(n, kThreads / lpr))), st, x, ldx, res, ldr, a, b, gamma, beta,
+  return launch_ln<LnFwd, T>(lpr, nc, dim3(ln_fwd_grid(n, d)), st, x, ldx, res, ldr, a, b, gamma, beta,
                              relu, eps, n, d, y, ldy, mean, rstd);
 }
 
@@ -1422,16 +1442,15 @@ int ln_bwd_t(const void* dy, int64_t lddy, const void* y, int64_t ldy, const voi
   if (sizeof(T) == 2 && ln8_width(d) &&
       ew8_rows(d, {{dy, lddy}, {relu ? y : nullptr, ldy}, {gamma ? x : nullptr, ldx}, {gamma ? res : nullptr, ldr}, {dx, lddx},
                    {dres, lddres}})) {
-    constexpr int R = 4;                                   // (2 / 4 / 8 rows in flight per lane measured 1.26 / 1.20 / 1.22 ms)
-    nblk = clamp_grid(ceil_div(n, kThreads / (d / 8) * R), kMaxStatBlocks);
+    nblk = ln8_bwd_grid(n, d);
     rc = by_ln8_lanes(d, [&](auto l) {
-      return launch(k_ln_bwd_bf16x8<decltype(l)::value, R>, dim3(nblk), st, dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma,
+      return launch(k_ln_bwd_bf16x8<decltype(l)::value, kLn8Rows>, dim3(nblk), st, dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma,
                     relu, mean, rstd, n, dx, lddx, dres, lddres, part);
     });
   } else {
     const int lpr = lanes_per_row(d);
     const int nc = (d + 4 * lpr - 1) / (4 * lpr);
-    nblk = clamp_grid(ceil_div(n, kThreads / lpr), kMaxStatBlocks);
+    nblk = ln_bwd_grid(n, d);
     rc = launch_ln<LnBwd, T>(lpr, nc, dim3(nblk), st, dy, lddy, y, ldy, x, ldx, res, ldr, a, b, gamma, relu, mean, rstd, n, d,
                              dx, lddx, dres, lddres, part);
   }
@@ -1815,7 +1834,7 @@ extern "C" int sgf_nll_fwd(const void* logits, int64_t ldl, int64_t n, int32_t c
   SGF_REQUIRE(logits && labels && idx, SGF_E_INVALID, "sgf_nll_fwd: null pointer");
   SGF_REQUIRE(workspace && workspace_bytes >= sgf_nll_workspace_bytes(m), SGF_E_WORKSPACE,
               "sgf_nll_fwd: workspace too small");
-  const int nblk = clamp_grid(ceil_div(m, 64), kNllMaxBlocks);
+  const int nblk = nll_fwd_blocks(m);
   float* part = static_cast<float*>(workspace);
   int rc = c <= 64   // one wave per 4 rows, or per row
                ? by_dtype(dtype, [&](auto t) { return launch(k_nll_fwd16<decltype(t)>, dim3(nblk), st, logits, ldl, c, labels, idx, m, part); })
@@ -1839,7 +1858,7 @@ extern "C" int sgf_nll_bwd(const void* logits, int64_t ldl, int64_t n, int32_t c
                                  static_cast<size_t>(n), st));
   if (m == 0) return SGF_OK;
   SGF_REQUIRE(logits && labels && idx, SGF_E_INVALID, "sgf_nll_bwd: null pointer");
-  const dim3 grid(clamp_grid(ceil_div(m, c <= 64 ? 16 : 4)));     // rows per block of the two kernels
+  const dim3 grid(nll_bwd_grid(m, c));
   if (c <= 64)
     return by_dtype(dtype, [&](auto t) {
       return launch(k_nll_bwd16<decltype(t)>, grid, st, logits, ldl, c, labels, idx, m, gout, inv_denom, dlogits, ldd);
@@ -1868,4 +1887,48 @@ extern "C" int sgf_colsum(const void* x, int64_t ldx, int64_t n, int32_t d, int3
   const int nblk = stat_blocks(n);
   int rc = by_dtype(dtype, [&](auto t) { return launch(k_colsum_any<decltype(t)>, dim3(nblk), st, x, ldx, n, d, workspace); });
   return rc != SGF_OK ? rc : sum_partials(static_cast<float*>(workspace), nblk, d, out, nullptr, d, st);
+}
+
+// Rows one loop iteration of the capped grid covers, for the persistent kernels of this file (include/sgf.h)
+extern "C" int64_t sgf_ew_lap_rows(int32_t kind, int32_t d, int32_t dtype, int32_t wide) {
+  if ((dtype != SGF_F32 && dtype != SGF_BF16) || (wide != 0 && wide != 1) || (wide && dtype != SGF_BF16) || d < 1) return -1;
+  const int64_t cap_n = static_cast<int64_t>(1) << 40;   // any n beyond the grid cap
+  const bool ew = d % 4 == 0 && d <= kMaxD;              // check_ew
+  switch (kind) {
+    case 0: case 1:                                      // sgf_ln_fwd, sgf_ln_bwd
+      if (!ew || (wide && !ln8_width(d))) return -1;
+      if (wide) return (kind == 0 ? ln8_fwd_grid(cap_n, d) : ln8_bwd_grid(cap_n, d)) * ln8_block_rows(d);
+      return (kind == 0 ? ln_fwd_grid(cap_n, d) : ln_bwd_grid(cap_n, d)) * ln_block_rows(d);
+    case 2: case 3:                                      // sgf_bn_apply, sgf_bn_bwd_apply
+      if (!ew || (wide && !ew8_width(d))) return -1;
+      return wide ? rowwalk8_grid(cap_n, d) * rowwalk8_block_rows(d) : rowwalk_grid(cap_n, d) * rowwalk_block_rows(d);
+    case 4: case 6:                                      // sgf_axpby; sgf_dropout, sgf_dropout_dev
+      if (!ew || wide) return -1;
+      return static_cast<int64_t>(ew_grid(cap_n * (d / 4))) * kThreads / (d / 4);
+    case 5:                                              // sgf_sum_n
+      if (!ew || (wide && d % 8 != 0)) return -1;
+      return wide ? static_cast<int64_t>(ew_grid(cap_n * (d / 8))) * kThreads / (d / 8)
+                  : static_cast<int64_t>(ew_grid(cap_n * (d / 4))) * kThreads / (d / 4);
+    case 7: {                                            // sgf_gather_rows: 4-column chunks when d % 4 == 0, else elements
+      if (wide || d > (1 << 20)) return -1;              // (cap_n * d must not overflow)
+      const int per_row = d % 4 == 0 ? d / 4 : d;
+      return static_cast<int64_t>(ew_grid(cap_n * per_row)) * kThreads / per_row;
+    }
+    case 8:                                              // sgf_pad_rows (d = d_pad): elements
+      if (wide || d > (1 << 20)) return -1;
+      return static_cast<int64_t>(ew_grid(cap_n * d)) * kThreads / d;
+    case 9:                                              // sgf_nll_bwd (d = c)
+      if (wide) return -1;
+      return nll_bwd_grid(cap_n, d) * nll_bwd_block_rows(d);
+    case 10:                                             // sgf_colstats, sgf_bn_bwd_stats, sgf_bn_bwd_stats2 (blocked)
+      if (!ew || (wide && !ew8_width(d))) return -1;
+      return static_cast<int64_t>(stat_blocks(cap_n)) * kStatBlockRows;
+    case 11:                                             // sgf_colsum (blocked)
+      if (wide || d > kThreads) return -1;
+      return static_cast<int64_t>(stat_blocks(cap_n)) * kStatBlockRows;
+    case 12:                                             // sgf_nll_fwd (d = c; blocked)
+      if (wide) return -1;
+      return static_cast<int64_t>(nll_fwd_blocks(cap_n)) * kNllBlockRows;
+    default: return -1;
+  }
 }

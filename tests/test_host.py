@@ -117,7 +117,7 @@ def test_every_entry_point_rejects_null_pointers_on_the_host():
     checked = 0
     for name, (_res, argtypes) in sorted(_lib.SIGNATURES.items()):
         if name in ("sgf_version", "sgf_last_error", "sgf_reload_env", "sgf_comm_available", "sgf_comm_destroy",
-                    "sgf_attn_max_blocks", "sgf_attn_tile_rows", "sgf_row_lap_rows", "sgf_spmm_arm", "sgf_spmm_blocked_arm") or \
+                    "sgf_attn_max_blocks", "sgf_attn_tile_rows", "sgf_row_lap_rows", "sgf_ew_lap_rows", "sgf_spmm_arm", "sgf_spmm_blocked_arm") or \
                 name.endswith(("_bytes", "_len", "_supported")):
             continue                                  # (queries; sgf_comm_destroy(NULL) is a no-op by contract)
         m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", src, flags=re.S)
