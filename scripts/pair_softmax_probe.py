@@ -107,14 +107,14 @@ def ratios(path):
 
 
 def resources(path):
-    """[(kernel, VGPRs, AGPRs, spilled VGPRs, scratch bytes per lane, waves per SIMD, LDS bytes)] of the k_ps_* kernels from the
+    """[(kernel, VGPRs, AGPRs, spilled VGPRs, scratch bytes per lane, waves per SIMD, LDS bytes)] of the softmax kernels (k_ps_fwd, k_pair_bwd_* with SoftmaxScore) from the
     compiler's remarks (hipcc ... -Rpass-analysis=kernel-resource-usage -c sgformer_amd/csrc/pair_attn.hip 2> FILE)"""
     import re
     rows = []
     if path and os.path.exists(path):
         for block in re.split(r"remark: [^\n]*Function Name: ", open(path).read())[1:]:
-            m = re.match(r"\S*?(k_ps_\w+?)I([ft])Li(\d+)E", block)
-            if m:
+            m = re.match(r"\S*?(k_ps_fwd|k_pair_bwd_\w+?)I([ft])Li(\d+)E(\S*)", block)
+            if m and (m.group(1) == "k_ps_fwd" or "SoftmaxScore" in m.group(4)):
                 get = lambda key: int(re.search(key + r": (\d+)", block).group(1))      # noqa: E731
                 rows.append((f"{m.group(1)}<{'fp32' if m.group(2) == 'f' else 'bf16'}, {m.group(3)}>", get("VGPRs"), get("AGPRs"),
                              get("VGPRs Spill"), get(r"ScratchSize \[bytes/lane\]"), get(r"Occupancy \[waves/SIMD\]"),

@@ -28,8 +28,9 @@
 //     compare on the row index, queries (bwd_kv) by a staged 1 / r = 0.  Resident rows past the end are clamped for the
 //     loads and never stored.
 //
-// The exact softmax attention (block N8, k_ps_*) is the second arm of this file: the same skeleton with an online maximum;
-// its comment stands in front of its kernels.
+// The exact softmax attention (block N8) is the second arm of this file: its forward (k_ps_fwd) is the same skeleton with
+// an online maximum, and its comment stands in front of it.  The two backward kernels (k_pair_bwd_q, k_pair_bwd_kv) serve
+// both arms: what differs between them is a score policy (SigmoidScore, SoftmaxScore).
 #include "common.h"
 
 namespace sgf {
@@ -45,7 +46,7 @@ struct PaArgs {
   int64_t ldq, ldk, ldv, ldg, ldo;
   void *out, *dq, *dk, *dv;
   int64_t ldout, lddq, lddk, lddv;
-  float* rowsum;                   // [n, heads]: written by fwd, read by the backward
+  float* rowsum;                   // [n, heads]: written by fwd, read by the backward (the softmax arm: lse)
   float* delta;                    // [n, heads]: written by bwd_q, read by bwd_kv
   int64_t n, l;
   int heads, v_heads;
@@ -246,122 +247,6 @@ __global__ __launch_bounds__(kPaThreads) void k_pa_fwd(const PaArgs p) {
   }
 }
 
-template <typename T, int D>
-__global__ __launch_bounds__(kPaThreads) void k_pa_bwd_q(const PaArgs p) {
-  constexpr int SW = pa_sweep<T, 1>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
-  __shared__ __attribute__((aligned(16))) T vs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T kt[I::kTr];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
-  const int64_t ic = i < p.n ? i : p.n - 1;
-  const T* kp = static_cast<const T*>(p.k) + h * D;
-  const T* vp = static_cast<const T*>(p.v) + hv * D;
-  typename I::Frag qf[I::kFrags], gf[I::kFrags];
-  I::load_frags(static_cast<const T*>(p.g) + ic * p.ldg + h * D, hh, gf);
-  float delta = I::dot_frags(gf, static_cast<const T*>(p.o) + ic * p.ldo + h * D, hh);
-  delta += __shfl_xor(delta, 32, 64);
-  if (i < p.n && hh == 0) p.delta[i * p.heads + h] = delta;
-  if (!p.dq) return;                                 // (uniform: delta only)
-  I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
-  const float rinv = 1.0f / p.rowsum[ic * p.heads + h];
-  f32x16 dq[D / 32];
-#pragma unroll
-  for (int t = 0; t < D / 32; ++t)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dq[t][q] = 0.f;
-  for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
-    I::template stage<true, true>(kp, p.ldk, j0, p.l, ks, kt);
-    I::template stage<true, false>(vp, p.ldv, j0, p.l, vs, nullptr);
-    __syncthreads();
-#pragma unroll
-    for (int st = 0; st < SW / 32; ++st) {
-      const int64_t lim = p.l - j0 - 32 * st;
-      if (lim > 0) {
-        f32x16 x = I::dot(ks, st, r, hh, qf);
-        const f32x16 pv = I::dot(vs, st, r, hh, gf);
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const float s = sigmoid<!I::kBf16>(x[q]);
-          const float dz = s * (1.0f - s) * ((pv[q] - delta) * rinv);
-          x[q] = slot_of(q, hh) < lim ? dz : 0.f;
-        }
-        I::acc(ks, kt, st, x, dq, r, hh);
-      }
-    }
-    __syncthreads();
-  }
-  if (i < p.n) I::template store<false>(static_cast<T*>(p.dq) + i * p.lddq + h * D, dq, hh, 1.f);
-}
-
-template <typename T, int D>
-__global__ __launch_bounds__(kPaThreads) void k_pa_bwd_kv(const PaArgs p) {
-  constexpr int SW = pa_sweep<T, 2>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T qs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T gs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T qt[I::kTr];
-  __shared__ __attribute__((aligned(16))) T gt[I::kTr];
-  __shared__ float rinv_s[SW], delta_s[SW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const bool shared_v = p.v_heads != p.heads;        // one value head: this workgroup walks every head, dv sums over them
-  const int h_begin = shared_v ? 0 : blockIdx.y, h_end = shared_v ? p.heads : h_begin + 1;
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
-  const int64_t jc = j < p.l ? j : p.l - 1;
-  typename I::Frag kf[I::kFrags], vf[I::kFrags];
-  I::load_frags(static_cast<const T*>(p.v) + jc * p.ldv + (shared_v ? 0 : h_begin) * D, hh, vf);
-  f32x16 dk[D / 32], dv[D / 32];
-#pragma unroll
-  for (int t = 0; t < D / 32; ++t)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dv[t][q] = 0.f;
-  for (int h = h_begin; h < h_end; ++h) {
-    I::load_frags(static_cast<const T*>(p.k) + jc * p.ldk + h * D, hh, kf);
-#pragma unroll
-    for (int t = 0; t < D / 32; ++t)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) dk[t][q] = 0.f;
-    const T* qp = static_cast<const T*>(p.q) + h * D;
-    const T* gp = static_cast<const T*>(p.g) + h * D;
-    for (int64_t i0 = 0; i0 < p.n; i0 += SW) {
-      I::template stage<true, true>(qp, p.ldq, i0, p.n, qs, qt);
-      I::template stage<true, true>(gp, p.ldg, i0, p.n, gs, gt);
-      if (threadIdx.x < SW) {
-        const int64_t i = i0 + threadIdx.x;
-        const bool in = i < p.n;
-        rinv_s[threadIdx.x] = in ? 1.0f / p.rowsum[i * p.heads + h] : 0.f;     // 0: a query row past the end adds nothing
-        delta_s[threadIdx.x] = in ? p.delta[i * p.heads + h] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int st = 0; st < SW / 32; ++st) {
-        if (p.n - i0 - 32 * st > 0) {
-          f32x16 x = I::dot(qs, st, r, hh, kf);
-          f32x16 pv = I::dot(gs, st, r, hh, vf);
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int sl = 32 * st + slot_of(q, hh);
-            const float ri = rinv_s[sl], de = delta_s[sl];
-            const float s = sigmoid<!I::kBf16>(x[q]);
-            x[q] = s * ri;
-            pv[q] = s * (1.0f - s) * ((pv[q] - de) * ri);
-          }
-          I::acc(gs, gt, st, x, dv, r, hh);
-          I::acc(qs, qt, st, pv, dk, r, hh);
-        }
-      }
-      __syncthreads();
-    }
-    if (j < p.l) {
-      I::template store<false>(static_cast<T*>(p.dk) + j * p.lddk + h * D, dk, hh, 1.f);
-      if (!shared_v) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv + h * D, dv, hh, 1.f);
-    }
-  }
-  if (shared_v && j < p.l) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv, dv, hh, 1.f);
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // The exact softmax arm (include/sgf.h block N8; medium/ablation/oursSOFT.py): the same skeleton, layout and staging with
 // an online maximum.  With z = scale q_i . k_j, per head:
@@ -464,8 +349,40 @@ __global__ __launch_bounds__(kPaThreads, D == 128 ? 2 : 1) void k_ps_fwd(const P
   }
 }
 
-template <typename T, int D>
-__global__ __launch_bounds__(kPaThreads) void k_ps_bwd_q(const PaArgs p, const float scale) {
+// ------------------------------------------------------------------------------------------------------------------------
+// The backward kernels of both arms.  They recompute the scores from q, k and the forward's saved fp32 row value (`rowsum`:
+// the sigmoid's r_i, the softmax's lse_i); a score policy holds what differs between the arms and nothing else:
+//   row_const(saved) : the per-row constant rc the pair formula uses (held per lane in bwd_q, staged in LDS in bwd_kv)
+//   kPastEnd         : rc of a swept query row past n (bwd_kv), chosen so that the row adds nothing
+//   bwd<kExact>(z = q_i . k_j, gv = g_i . v_j, delta_i, rc, scale) -> w, the weight of g_i in dv_j, and dz = dL/dz;
+//                      kExact: fp32 storage (expf), else the hardware exp2
+// The expressions are kept as one statement each: the compiler contracts multiplies and adds inside a statement.
+struct SigmoidScore {
+  static constexpr float kPastEnd = 0.f;             // 1 / r = 0: w = dz = 0 (the staged zero rows alone would score 0.5)
+  static __device__ __forceinline__ float row_const(float rowsum) { return 1.0f / rowsum; }
+  // dZ = S (1 - S) (g . v - delta) / r.  1 - S is formed from S, so a saturated score has an exactly zero derivative
+  template <bool kExact>
+  static __device__ __forceinline__ void bwd(float z, float gv, float delta, float rinv, float, float& w, float& dz) {
+    const float s = sigmoid<kExact>(z);
+    w = s * rinv;
+    dz = s * (1.0f - s) * ((gv - delta) * rinv);
+  }
+};
+
+struct SoftmaxScore {
+  static constexpr float kPastEnd = INFINITY;        // lse = +inf: P = exp(0 - inf) = 0, and the row's g is zeros
+  static __device__ __forceinline__ float row_const(float lse) { return lse; }
+  // P = exp(scale z - lse): no running maximum.  dZ = scale P (g . v - delta)
+  template <bool kExact>
+  static __device__ __forceinline__ void bwd(float z, float gv, float delta, float lse, float scale, float& w, float& dz) {
+    const float pr = pa_exp<kExact>(scale * z - lse);
+    w = pr;
+    dz = scale * pr * (gv - delta);
+  }
+};
+
+template <typename T, int D, typename Score>
+__global__ __launch_bounds__(kPaThreads) void k_pair_bwd_q(const PaArgs p, const float scale) {
   constexpr int SW = pa_sweep<T, 1>();
   using I = PaImg<T, D, SW>;
   __shared__ __attribute__((aligned(16))) T ks[I::kRm];
@@ -484,7 +401,7 @@ __global__ __launch_bounds__(kPaThreads) void k_ps_bwd_q(const PaArgs p, const f
   if (i < p.n && hh == 0) p.delta[i * p.heads + h] = delta;
   if (!p.dq) return;                                 // (uniform: delta only)
   I::load_frags(static_cast<const T*>(p.q) + ic * p.ldq + h * D, hh, qf);
-  const float lse = p.rowsum[ic * p.heads + h];
+  const float rc = Score::row_const(p.rowsum[ic * p.heads + h]);
   f32x16 dq[D / 32];
 #pragma unroll
   for (int t = 0; t < D / 32; ++t)
@@ -502,8 +419,9 @@ __global__ __launch_bounds__(kPaThreads) void k_ps_bwd_q(const PaArgs p, const f
         const f32x16 pv = I::dot(vs, st, r, hh, gf);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const float pr = pa_exp<!I::kBf16>(scale * x[q] - lse);
-          x[q] = slot_of(q, hh) < lim ? scale * pr * (pv[q] - delta) : 0.f;
+          float w, dz;
+          Score::template bwd<!I::kBf16>(x[q], pv[q], delta, rc, scale, w, dz);
+          x[q] = slot_of(q, hh) < lim ? dz : 0.f;
         }
         I::acc(ks, kt, st, x, dq, r, hh);
       }
@@ -513,15 +431,15 @@ __global__ __launch_bounds__(kPaThreads) void k_ps_bwd_q(const PaArgs p, const f
   if (i < p.n) I::template store<false>(static_cast<T*>(p.dq) + i * p.lddq + h * D, dq, hh, 1.f);
 }
 
-template <typename T, int D>
-__global__ __launch_bounds__(kPaThreads) void k_ps_bwd_kv(const PaArgs p, const float scale) {
+template <typename T, int D, typename Score>
+__global__ __launch_bounds__(kPaThreads) void k_pair_bwd_kv(const PaArgs p, const float scale) {
   constexpr int SW = pa_sweep<T, 2>();
   using I = PaImg<T, D, SW>;
   __shared__ __attribute__((aligned(16))) T qs[I::kRm];
   __shared__ __attribute__((aligned(16))) T gs[I::kRm];
   __shared__ __attribute__((aligned(16))) T qt[I::kTr];
   __shared__ __attribute__((aligned(16))) T gt[I::kTr];
-  __shared__ float lse_s[SW], delta_s[SW];
+  __shared__ float rc_s[SW], delta_s[SW];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const bool shared_v = p.v_heads != p.heads;        // one value head: this workgroup walks every head, dv sums over them
   const int h_begin = shared_v ? 0 : blockIdx.y, h_end = shared_v ? p.heads : h_begin + 1;
@@ -548,7 +466,7 @@ __global__ __launch_bounds__(kPaThreads) void k_ps_bwd_kv(const PaArgs p, const 
       if (threadIdx.x < SW) {
         const int64_t i = i0 + threadIdx.x;
         const bool in = i < p.n;
-        lse_s[threadIdx.x] = in ? p.rowsum[i * p.heads + h] : INFINITY;      // +inf: a query row past the end has P = 0
+        rc_s[threadIdx.x] = in ? Score::row_const(p.rowsum[i * p.heads + h]) : Score::kPastEnd;   // past the end: adds nothing
         delta_s[threadIdx.x] = in ? p.delta[i * p.heads + h] : 0.f;
       }
       __syncthreads();
@@ -560,9 +478,11 @@ __global__ __launch_bounds__(kPaThreads) void k_ps_bwd_kv(const PaArgs p, const 
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             const int sl = 32 * st + slot_of(q, hh);
-            const float pr = pa_exp<!I::kBf16>(scale * x[q] - lse_s[sl]);
-            x[q] = pr;
-            pv[q] = scale * pr * (pv[q] - delta_s[sl]);
+            const float rc = rc_s[sl], de = delta_s[sl];
+            float w, dz;
+            Score::template bwd<!I::kBf16>(x[q], pv[q], de, rc, scale, w, dz);
+            x[q] = w;
+            pv[q] = dz;
           }
           I::acc(gs, gt, st, x, dv, r, hh);
           I::acc(qs, qt, st, pv, dk, r, hh);
@@ -619,161 +539,169 @@ int check_pa_rows(const char* fn, const PaOperand* ops, int count, int dtype) {
   return SGF_OK;
 }
 
+// The two arms of the entries: what the forward saves per row, and what l == 0 would ask for.
+struct PaArm {
+  bool softmax;
+  const char *saved, *no_keys;
+};
+constexpr PaArm kSigmoidArm = {false, "rowsum", "a row sum over no keys"};
+constexpr PaArm kSoftmaxArm = {true, "lse", "a softmax over no keys"};
+
+// check_pa, then the score scale of the softmax arm
+int check_pa_arm(const char* fn, const PaArm& arm, float scale, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype) {
+  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  SGF_REQUIRE(!arm.softmax || (std::isfinite(scale) && scale > 0.f), SGF_E_INVALID, "%s: scale must be finite and positive (%g)",
+              fn, static_cast<double>(scale));
+  return SGF_OK;
+}
+
+// one launch over the storage dtype, the width and the arm; the score scale is the second kernel argument of every kernel but
+// the sigmoid forward (the sigmoid policy never reads it)
 template <template <typename, int> class Launch>
-int pa_dispatch(int d, int dtype, const PaArgs& a, dim3 grid, hipStream_t st) {
+int pa_dispatch(const PaArm& arm, int d, int dtype, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    if (d == 32) Launch<T, 32>::run(a, grid, st);
-    else if (d == 64) Launch<T, 64>::run(a, grid, st);
-    else Launch<T, 128>::run(a, grid, st);
+    if (d == 32) Launch<T, 32>::run(arm.softmax, a, scale, grid, st);
+    else if (d == 64) Launch<T, 64>::run(arm.softmax, a, scale, grid, st);
+    else Launch<T, 128>::run(arm.softmax, a, scale, grid, st);
     SGF_LAUNCH_CHECK();
     return static_cast<int>(SGF_OK);
   });
 }
 template <typename T, int D>
 struct PaFwd {
-  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_pa_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  static void run(bool softmax, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    if (softmax) hipLaunchKernelGGL((k_ps_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
+    else hipLaunchKernelGGL((k_pa_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a);
   }
 };
 template <typename T, int D>
 struct PaBwdQ {
-  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_pa_bwd_q<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  static void run(bool softmax, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    if (softmax) hipLaunchKernelGGL((k_pair_bwd_q<T, D, SoftmaxScore>), grid, dim3(kPaThreads), 0, st, a, scale);
+    else hipLaunchKernelGGL((k_pair_bwd_q<T, D, SigmoidScore>), grid, dim3(kPaThreads), 0, st, a, scale);
   }
 };
 template <typename T, int D>
 struct PaBwdKv {
-  static void run(const PaArgs& a, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_pa_bwd_kv<T, D>), grid, dim3(kPaThreads), 0, st, a);
+  static void run(bool softmax, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
+    if (softmax) hipLaunchKernelGGL((k_pair_bwd_kv<T, D, SoftmaxScore>), grid, dim3(kPaThreads), 0, st, a, scale);
+    else hipLaunchKernelGGL((k_pair_bwd_kv<T, D, SigmoidScore>), grid, dim3(kPaThreads), 0, st, a, scale);
   }
 };
-
-// the softmax arm: the same dispatch with the score scale as a second kernel argument
-template <template <typename, int> class Launch>
-int ps_dispatch(int d, int dtype, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
-  return by_dtype(dtype, [&](auto t) {
-    using T = decltype(t);
-    if (d == 32) Launch<T, 32>::run(a, scale, grid, st);
-    else if (d == 64) Launch<T, 64>::run(a, scale, grid, st);
-    else Launch<T, 128>::run(a, scale, grid, st);
-    SGF_LAUNCH_CHECK();
-    return static_cast<int>(SGF_OK);
-  });
-}
-template <typename T, int D>
-struct PsFwd {
-  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_ps_fwd<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
-  }
-};
-template <typename T, int D>
-struct PsBwdQ {
-  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_ps_bwd_q<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
-  }
-};
-template <typename T, int D>
-struct PsBwdKv {
-  static void run(const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
-    hipLaunchKernelGGL((k_ps_bwd_kv<T, D>), grid, dim3(kPaThreads), 0, st, a, scale);
-  }
-};
-
-// sizes, shape and the score scale of the three softmax launches
-int check_ps(const char* fn, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype, float scale) {
-  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
-  SGF_REQUIRE(std::isfinite(scale) && scale > 0.f, SGF_E_INVALID, "%s: scale must be finite and positive (%g)", fn,
-              static_cast<double>(scale));
-  return SGF_OK;
-}
 
 inline unsigned pa_tiles(int64_t rows) { return static_cast<unsigned>((rows + kPaRows - 1) / kPaRows); }
+
+// delta fp32 [n, heads]; nothing of size l, nothing of size n x l
+size_t pa_workspace_bytes(int64_t n, int64_t l, int heads) {
+  if (n < 0 || l < 0 || heads < 1) return 0;
+  return static_cast<size_t>(n) * heads * sizeof(float);
+}
+
+int64_t pa_lap_rows(const char* fn, int which, int heads, int d, int dtype, int laps) {
+  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
+    set_error("%s: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", fn, which, laps, heads, d, dtype);
+    return -1;
+  }
+  return 0;      // every workgroup of the three kernels owns one resident tile: there is no second lap
+}
+
+// The three launches of both arms (`saved`: rowsum or lse).  Order of the checks: sizes, head counts, shape and dtype, the
+// softmax's scale; n == 0 is a no-op; l == 0; null pointers, widths, alignment; `saved`; the workspace.
+int pa_fwd(const char* fn, const PaArm& arm, float scale, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+           int64_t ldv, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype, void* out, int64_t ldo, float* saved,
+           void* stream) {
+  if (int rc = check_pa_arm(fn, arm, scale, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (%s)", fn, arm.no_keys);
+  const PaOperand ops[] = {{"q", q, ldq, heads * d}, {"k", k, ldk, heads * d}, {"v", v, ldv, v_heads * d}, {"out", out, ldo, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 4, dtype)) return rc;
+  SGF_REQUIRE(saved, SGF_E_INVALID, "%s: null pointer (%s)", fn, arm.saved);
+  PaArgs a = {};
+  a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv, a.out = out, a.ldout = ldo, a.rowsum = saved;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaFwd>(arm, d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+int pa_bwd_q(const char* fn, const PaArm& arm, float scale, const void* g, int64_t ldg, const void* out, int64_t ldo,
+             const float* saved, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n,
+             int64_t l, int heads, int v_heads, int d, int dtype, void* dq, int64_t lddq, void* workspace, size_t workspace_bytes,
+             void* stream) {
+  if (int rc = check_pa_arm(fn, arm, scale, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (%s)", fn, arm.no_keys);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"out", out, ldo, heads * d}, {"q", q, ldq, heads * d},
+                           {"k", k, ldk, heads * d},   {"v", v, ldv, v_heads * d},   {"dq", dq, lddq, heads * d}};
+  if (int rc = check_pa_rows(fn, ops, dq ? 6 : 5, dtype)) return rc;      // dq == NULL: delta only
+  SGF_REQUIRE(saved, SGF_E_INVALID, "%s: null pointer (%s)", fn, arm.saved);
+  SGF_REQUIRE(workspace && workspace_bytes >= pa_workspace_bytes(n, l, heads), SGF_E_WORKSPACE, "%s: workspace %zu < %zu", fn,
+              workspace ? workspace_bytes : static_cast<size_t>(0), pa_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.o = out, a.ldo = ldo, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(saved), a.delta = static_cast<float*>(workspace), a.dq = dq, a.lddq = lddq;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaBwdQ>(arm, d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+}
+
+int pa_bwd_kv(const char* fn, const PaArm& arm, float scale, const void* g, int64_t ldg, const float* saved, const void* q,
+              int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int heads, int v_heads,
+              int d, int dtype, void* dk, int64_t lddk, void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes,
+              void* stream) {
+  if (int rc = check_pa_arm(fn, arm, scale, n, l, heads, v_heads, d, dtype)) return rc;
+  if (n == 0) return SGF_OK;
+  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (%s)", fn, arm.no_keys);
+  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"q", q, ldq, heads * d},     {"k", k, ldk, heads * d},
+                           {"v", v, ldv, v_heads * d}, {"dk", dk, lddk, heads * d},  {"dv", dv, lddv, v_heads * d}};
+  if (int rc = check_pa_rows(fn, ops, 6, dtype)) return rc;
+  SGF_REQUIRE(saved, SGF_E_INVALID, "%s: null pointer (%s)", fn, arm.saved);
+  SGF_REQUIRE(workspace && workspace_bytes >= pa_workspace_bytes(n, l, heads), SGF_E_WORKSPACE, "%s: workspace %zu < %zu", fn,
+              workspace ? workspace_bytes : static_cast<size_t>(0), pa_workspace_bytes(n, l, heads));
+  PaArgs a = {};
+  a.g = g, a.ldg = ldg, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
+  a.rowsum = const_cast<float*>(saved), a.delta = static_cast<float*>(const_cast<void*>(workspace));
+  a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
+  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
+  return pa_dispatch<PaBwdKv>(arm, d, dtype, a, scale, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
+                              static_cast<hipStream_t>(stream));
+}
 
 }  // namespace
 }  // namespace sgf
 
 using namespace sgf;
 
+// ---- block N7: the sigmoid arm ---------------------------------------------------------------------------------------
 extern "C" int32_t sgf_pair_sigmoid_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype) {
   return pa_shape_ok(heads, v_heads, d, dtype) ? 1 : 0;
 }
 
-// delta fp32 [n, heads]; nothing of size l, nothing of size n x l
-extern "C" size_t sgf_pair_sigmoid_workspace_bytes(int64_t n, int64_t l, int32_t heads) {
-  if (n < 0 || l < 0 || heads < 1) return 0;
-  return static_cast<size_t>(n) * heads * sizeof(float);
-}
+extern "C" size_t sgf_pair_sigmoid_workspace_bytes(int64_t n, int64_t l, int32_t heads) { return pa_workspace_bytes(n, l, heads); }
 
 extern "C" int64_t sgf_pair_sigmoid_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
-  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
-    set_error("sgf_pair_sigmoid_lap_rows: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", which, laps,
-              heads, d, dtype);
-    return -1;
-  }
-  return 0;      // every workgroup of the three kernels owns one resident tile: there is no second lap
+  return pa_lap_rows("sgf_pair_sigmoid_lap_rows", which, heads, d, dtype, laps);
 }
 
 extern "C" int sgf_pair_sigmoid_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                     int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* out,
                                     int64_t ldo, float* rowsum, void* stream) {
-  const char* fn = "sgf_pair_sigmoid_fwd";
-  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
-  const PaOperand ops[] = {{"q", q, ldq, heads * d}, {"k", k, ldk, heads * d}, {"v", v, ldv, v_heads * d}, {"out", out, ldo, heads * d}};
-  if (int rc = check_pa_rows(fn, ops, 4, dtype)) return rc;
-  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
-  PaArgs a = {};
-  a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv, a.out = out, a.ldout = ldo, a.rowsum = rowsum;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return pa_dispatch<PaFwd>(d, dtype, a, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+  return pa_fwd("sgf_pair_sigmoid_fwd", kSigmoidArm, 1.0f, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d, dtype, out, ldo,
+                rowsum, stream);
 }
 
 extern "C" int sgf_pair_sigmoid_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* rowsum,
                                       const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                       int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dq,
                                       int64_t lddq, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "sgf_pair_sigmoid_bwd_q";
-  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
-  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"out", out, ldo, heads * d}, {"q", q, ldq, heads * d},
-                           {"k", k, ldk, heads * d},   {"v", v, ldv, v_heads * d},   {"dq", dq, lddq, heads * d}};
-  if (int rc = check_pa_rows(fn, ops, dq ? 6 : 5, dtype)) return rc;      // dq == NULL: delta only
-  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_sigmoid_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
-              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
-              sgf_pair_sigmoid_workspace_bytes(n, l, heads));
-  PaArgs a = {};
-  a.g = g, a.ldg = ldg, a.o = out, a.ldo = ldo, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
-  a.rowsum = const_cast<float*>(rowsum), a.delta = static_cast<float*>(workspace), a.dq = dq, a.lddq = lddq;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return pa_dispatch<PaBwdQ>(d, dtype, a, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+  return pa_bwd_q("sgf_pair_sigmoid_bwd_q", kSigmoidArm, 1.0f, g, ldg, out, ldo, rowsum, q, ldq, k, ldk, v, ldv, n, l, heads,
+                  v_heads, d, dtype, dq, lddq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* rowsum, const void* q, int64_t ldq,
                                        const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
                                        int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dk, int64_t lddk,
                                        void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "sgf_pair_sigmoid_bwd_kv";
-  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a row sum over no keys)", fn);
-  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"q", q, ldq, heads * d},     {"k", k, ldk, heads * d},
-                           {"v", v, ldv, v_heads * d}, {"dk", dk, lddk, heads * d},  {"dv", dv, lddv, v_heads * d}};
-  if (int rc = check_pa_rows(fn, ops, 6, dtype)) return rc;
-  SGF_REQUIRE(rowsum, SGF_E_INVALID, "%s: null pointer (rowsum)", fn);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_sigmoid_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
-              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
-              sgf_pair_sigmoid_workspace_bytes(n, l, heads));
-  PaArgs a = {};
-  a.g = g, a.ldg = ldg, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
-  a.rowsum = const_cast<float*>(rowsum), a.delta = static_cast<float*>(const_cast<void*>(workspace));
-  a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return pa_dispatch<PaBwdKv>(d, dtype, a, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
-                              static_cast<hipStream_t>(stream));
+  return pa_bwd_kv("sgf_pair_sigmoid_bwd_kv", kSigmoidArm, 1.0f, g, ldg, rowsum, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d,
+                   dtype, dk, lddk, dv, lddv, workspace, workspace_bytes, stream);
 }
 
 // ---- block N8: the exact softmax arm ---------------------------------------------------------------------------------
@@ -781,35 +709,17 @@ extern "C" int32_t sgf_pair_softmax_supported(int32_t heads, int32_t v_heads, in
   return pa_shape_ok(heads, v_heads, d, dtype) ? 1 : 0;
 }
 
-// delta fp32 [n, heads]; nothing of size l, nothing of size n x l
-extern "C" size_t sgf_pair_softmax_workspace_bytes(int64_t n, int64_t l, int32_t heads) {
-  if (n < 0 || l < 0 || heads < 1) return 0;
-  return static_cast<size_t>(n) * heads * sizeof(float);
-}
+extern "C" size_t sgf_pair_softmax_workspace_bytes(int64_t n, int64_t l, int32_t heads) { return pa_workspace_bytes(n, l, heads); }
 
 extern "C" int64_t sgf_pair_softmax_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
-  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
-    set_error("sgf_pair_softmax_lap_rows: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", which, laps,
-              heads, d, dtype);
-    return -1;
-  }
-  return 0;      // every workgroup of the three kernels owns one resident tile: there is no second lap
+  return pa_lap_rows("sgf_pair_softmax_lap_rows", which, heads, d, dtype, laps);
 }
 
 extern "C" int sgf_pair_softmax_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                     int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale,
                                     void* out, int64_t ldo, float* lse, void* stream) {
-  const char* fn = "sgf_pair_softmax_fwd";
-  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
-  const PaOperand ops[] = {{"q", q, ldq, heads * d}, {"k", k, ldk, heads * d}, {"v", v, ldv, v_heads * d}, {"out", out, ldo, heads * d}};
-  if (int rc = check_pa_rows(fn, ops, 4, dtype)) return rc;
-  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
-  PaArgs a = {};
-  a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv, a.out = out, a.ldout = ldo, a.rowsum = lse;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return ps_dispatch<PsFwd>(d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+  return pa_fwd("sgf_pair_softmax_fwd", kSoftmaxArm, scale, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d, dtype, out, ldo, lse,
+                stream);
 }
 
 extern "C" int sgf_pair_softmax_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* lse,
@@ -817,22 +727,8 @@ extern "C" int sgf_pair_softmax_bwd_q(const void* g, int64_t ldg, const void* ou
                                       int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype,
                                       float scale, void* dq, int64_t lddq, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  const char* fn = "sgf_pair_softmax_bwd_q";
-  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
-  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"out", out, ldo, heads * d}, {"q", q, ldq, heads * d},
-                           {"k", k, ldk, heads * d},   {"v", v, ldv, v_heads * d},   {"dq", dq, lddq, heads * d}};
-  if (int rc = check_pa_rows(fn, ops, dq ? 6 : 5, dtype)) return rc;      // dq == NULL: delta only
-  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_softmax_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
-              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
-              sgf_pair_softmax_workspace_bytes(n, l, heads));
-  PaArgs a = {};
-  a.g = g, a.ldg = ldg, a.o = out, a.ldo = ldo, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
-  a.rowsum = const_cast<float*>(lse), a.delta = static_cast<float*>(workspace), a.dq = dq, a.lddq = lddq;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return ps_dispatch<PsBwdQ>(d, dtype, a, scale, dim3(pa_tiles(n), heads), static_cast<hipStream_t>(stream));
+  return pa_bwd_q("sgf_pair_softmax_bwd_q", kSoftmaxArm, scale, g, ldg, out, ldo, lse, q, ldq, k, ldk, v, ldv, n, l, heads,
+                  v_heads, d, dtype, dq, lddq, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* lse, const void* q, int64_t ldq,
@@ -840,22 +736,6 @@ extern "C" int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* 
                                        int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* dk,
                                        int64_t lddk, void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes,
                                        void* stream) {
-  const char* fn = "sgf_pair_softmax_bwd_kv";
-  if (int rc = check_ps(fn, n, l, heads, v_heads, d, dtype, scale)) return rc;
-  if (n == 0) return SGF_OK;
-  SGF_REQUIRE(l > 0, SGF_E_INVALID, "%s: l == 0 (a softmax over no keys)", fn);
-  const PaOperand ops[] = {{"g", g, ldg, heads * d},   {"q", q, ldq, heads * d},     {"k", k, ldk, heads * d},
-                           {"v", v, ldv, v_heads * d}, {"dk", dk, lddk, heads * d},  {"dv", dv, lddv, v_heads * d}};
-  if (int rc = check_pa_rows(fn, ops, 6, dtype)) return rc;
-  SGF_REQUIRE(lse, SGF_E_INVALID, "%s: null pointer (lse)", fn);
-  SGF_REQUIRE(workspace && workspace_bytes >= sgf_pair_softmax_workspace_bytes(n, l, heads), SGF_E_WORKSPACE,
-              "%s: workspace %zu < %zu", fn, workspace ? workspace_bytes : static_cast<size_t>(0),
-              sgf_pair_softmax_workspace_bytes(n, l, heads));
-  PaArgs a = {};
-  a.g = g, a.ldg = ldg, a.q = q, a.ldq = ldq, a.k = k, a.ldk = ldk, a.v = v, a.ldv = ldv;
-  a.rowsum = const_cast<float*>(lse), a.delta = static_cast<float*>(const_cast<void*>(workspace));
-  a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
-  a.n = n, a.l = l, a.heads = heads, a.v_heads = v_heads;
-  return ps_dispatch<PsBwdKv>(d, dtype, a, scale, dim3(pa_tiles(l), v_heads == heads ? heads : 1),
-                              static_cast<hipStream_t>(stream));
+  return pa_bwd_kv("sgf_pair_softmax_bwd_kv", kSoftmaxArm, scale, g, ldg, lse, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d,
+                   dtype, dk, lddk, dv, lddv, workspace, workspace_bytes, stream);
 }

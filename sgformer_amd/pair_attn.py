@@ -52,83 +52,89 @@ SOFTMAX_MIN_PAIRS = 40000 * 40000 * 2        # fp32 storage
 SOFTMAX_MIN_PAIRS_BF16 = 40000 * 40000 * 2   # bf16 storage
 
 
+# The two arms.  An arm is told by its entry family ("pair_sigmoid" / "pair_softmax": the prefix of the sgf_* entries and of the
+# kernel table's methods); here is what else differs: the public function's name, its switch and its two thresholds (module
+# attributes, looked up by name on every call).
+_ARMS = {"pair_sigmoid": ("sigmoid_attention", "SGF_PAIR_ATTN", "PAIR_MIN_PAIRS", "PAIR_MIN_PAIRS_BF16"),
+         "pair_softmax": ("softmax_attention", "SGF_PAIR_SOFTMAX", "SOFTMAX_MIN_PAIRS", "SOFTMAX_MIN_PAIRS_BF16")}
+
+
 # ------------------------------------------------------------------------------------------------
 # the entries on the current stream (private: the kernel table of kernels.py is not extended)
 # ------------------------------------------------------------------------------------------------
+def _hip_supported(family: str, heads: int, v_heads: int, d: int, dtype) -> bool:
+    if dtype not in (_F32, _BF16):
+        return False
+    return bool(getattr(_lib.load(), f"sgf_{family}_supported")(int(heads), int(v_heads), int(d),
+                                                                _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+
+
+# `scale`: () for the sigmoid entries, (scale,) for the softmax entries, whose argument lists have it after the dtype code
+def _hip_fwd(family: str, scale: tuple, q, k, v):
+    dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
+    out = torch.empty((n, h, d), dtype=q.dtype, device=dev)
+    saved = torch.empty((n, h), dtype=_F32, device=dev)
+    _launch(dev, f"sgf_{family}_fwd", q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, _code(q), *scale, out,
+            h * d, saved)
+    return out, saved
+
+
+def _hip_bwd_q(family: str, scale: tuple, g, out, saved, q, k, v, want_dq: bool):
+    dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
+    dq = torch.empty((n, h, d), dtype=q.dtype, device=dev) if want_dq else None
+    delta = torch.empty((n, h), dtype=_F32, device=dev)
+    _launch(dev, f"sgf_{family}_bwd_q", g, g.stride(0), out, out.stride(0), saved, q, q.stride(0), k, k.stride(0), v,
+            v.stride(0), n, l, h, hv, d, _code(q), *scale, dq, h * d, delta, delta.numel() * 4)
+    return dq, delta
+
+
+def _hip_bwd_kv(family: str, scale: tuple, g, saved, delta, q, k, v):
+    dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
+    dk = torch.empty((l, h, d), dtype=q.dtype, device=dev)
+    dv = torch.empty((l, hv, d), dtype=q.dtype, device=dev)
+    _launch(dev, f"sgf_{family}_bwd_kv", g, g.stride(0), saved, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d,
+            _code(q), *scale, dk, h * d, dv, hv * d, delta, delta.numel() * 4)
+    return dk, dv
+
+
 class _Hip:
     @staticmethod
     def pair_sigmoid_supported(heads: int, v_heads: int, d: int, dtype) -> bool:
-        if dtype not in (_F32, _BF16):
-            return False
-        return bool(_lib.load().sgf_pair_sigmoid_supported(int(heads), int(v_heads), int(d),
-                                                           _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+        return _hip_supported("pair_sigmoid", heads, v_heads, d, dtype)
 
     @staticmethod
     def pair_sigmoid_fwd(q, k, v):
         """(out [n, H, D] in the storage dtype, rowsum fp32 [n, H])"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        out = torch.empty((n, h, d), dtype=q.dtype, device=dev)
-        rowsum = torch.empty((n, h), dtype=_F32, device=dev)
-        _launch(dev, "sgf_pair_sigmoid_fwd", q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, _code(q), out,
-                h * d, rowsum)
-        return out, rowsum
+        return _hip_fwd("pair_sigmoid", (), q, k, v)
 
     @staticmethod
     def pair_sigmoid_bwd_q(g, out, rowsum, q, k, v, want_dq: bool = True):
         """(dq [n, H, D] or None, delta fp32 [n, H] = g . out per row and head: the operand of pair_sigmoid_bwd_kv)"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        dq = torch.empty((n, h, d), dtype=q.dtype, device=dev) if want_dq else None
-        delta = torch.empty((n, h), dtype=_F32, device=dev)
-        _launch(dev, "sgf_pair_sigmoid_bwd_q", g, g.stride(0), out, out.stride(0), rowsum, q, q.stride(0), k, k.stride(0), v,
-                v.stride(0), n, l, h, hv, d, _code(q), dq, h * d, delta, delta.numel() * 4)
-        return dq, delta
+        return _hip_bwd_q("pair_sigmoid", (), g, out, rowsum, q, k, v, want_dq)
 
     @staticmethod
     def pair_sigmoid_bwd_kv(g, rowsum, delta, q, k, v):
         """(dk [l, H, D], dv [l, Hv, D]; Hv = 1: dv summed over the heads)"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        dk = torch.empty((l, h, d), dtype=q.dtype, device=dev)
-        dv = torch.empty((l, hv, d), dtype=q.dtype, device=dev)
-        _launch(dev, "sgf_pair_sigmoid_bwd_kv", g, g.stride(0), rowsum, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l,
-                h, hv, d, _code(q), dk, h * d, dv, hv * d, delta, delta.numel() * 4)
-        return dk, dv
+        return _hip_bwd_kv("pair_sigmoid", (), g, rowsum, delta, q, k, v)
 
     @staticmethod
     def pair_softmax_supported(heads: int, v_heads: int, d: int, dtype) -> bool:
-        if dtype not in (_F32, _BF16):
-            return False
-        return bool(_lib.load().sgf_pair_softmax_supported(int(heads), int(v_heads), int(d),
-                                                           _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
+        return _hip_supported("pair_softmax", heads, v_heads, d, dtype)
 
     @staticmethod
     def pair_softmax_fwd(q, k, v, scale: float = 1.0):
         """(out [n, H, D] in the storage dtype, lse fp32 [n, H])"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        out = torch.empty((n, h, d), dtype=q.dtype, device=dev)
-        lse = torch.empty((n, h), dtype=_F32, device=dev)
-        _launch(dev, "sgf_pair_softmax_fwd", q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, _code(q),
-                float(scale), out, h * d, lse)
-        return out, lse
+        return _hip_fwd("pair_softmax", (float(scale),), q, k, v)
 
     @staticmethod
     def pair_softmax_bwd_q(g, out, lse, q, k, v, scale: float = 1.0, want_dq: bool = True):
         """(dq [n, H, D] or None, delta fp32 [n, H] = g . out per row and head: the operand of pair_softmax_bwd_kv)"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        dq = torch.empty((n, h, d), dtype=q.dtype, device=dev) if want_dq else None
-        delta = torch.empty((n, h), dtype=_F32, device=dev)
-        _launch(dev, "sgf_pair_softmax_bwd_q", g, g.stride(0), out, out.stride(0), lse, q, q.stride(0), k, k.stride(0), v,
-                v.stride(0), n, l, h, hv, d, _code(q), float(scale), dq, h * d, delta, delta.numel() * 4)
-        return dq, delta
+        return _hip_bwd_q("pair_softmax", (float(scale),), g, out, lse, q, k, v, want_dq)
 
     @staticmethod
     def pair_softmax_bwd_kv(g, lse, delta, q, k, v, scale: float = 1.0):
         """(dk [l, H, D], dv [l, Hv, D]; Hv = 1: dv summed over the heads)"""
-        dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
-        dk = torch.empty((l, h, d), dtype=q.dtype, device=dev)
-        dv = torch.empty((l, hv, d), dtype=q.dtype, device=dev)
-        _launch(dev, "sgf_pair_softmax_bwd_kv", g, g.stride(0), lse, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l,
-                h, hv, d, _code(q), float(scale), dk, h * d, dv, hv * d, delta, delta.numel() * 4)
-        return dk, dv
+        return _hip_bwd_kv("pair_softmax", (float(scale),), g, lse, delta, q, k, v)
 
 
 def _table(entry: str = "pair_sigmoid_fwd"):
@@ -143,12 +149,6 @@ def _table(entry: str = "pair_sigmoid_fwd"):
 # ------------------------------------------------------------------------------------------------
 # which calls the kernels take
 # ------------------------------------------------------------------------------------------------
-def supported(q, k, v) -> bool:
-    """q [n, H, D], k [l, H, D], v [l, H | 1, D]: tensors of one dtype on the GPU, contiguous in the last dimension, in a
-    shape the library accepts, with at least one query and one key, and a kernel table that has the entries."""
-    return _supported(q, k, v, "pair_sigmoid")
-
-
 def _supported(q, k, v, family: str) -> bool:
     t = _table(family + "_fwd")
     if t is None or not all(torch.is_tensor(x) and x.dim() == 3 for x in (q, k, v)):
@@ -165,14 +165,38 @@ def _supported(q, k, v, family: str) -> bool:
     return bool(getattr(t, family + "_supported")(h, hv, d, q.dtype))
 
 
+def _use(q, k, v, family: str) -> bool:
+    """_supported under the arm's switch (read on every call): 0 = always the dense path, 1 = the kernels wherever supported,
+    unset = the kernels from the arm's threshold for the storage dtype (n l H score entries) upward."""
+    _, switch, min_pairs, min_pairs_bf16 = _ARMS[family]
+    s = os.environ.get(switch)
+    if s is not None and not _switch(switch, True):
+        return False
+    if not _supported(q, k, v, family):
+        return False
+    return s is not None or q.shape[0] * k.shape[0] * q.shape[1] >= globals()[min_pairs_bf16 if q.dtype == _BF16 else min_pairs]
+
+
+def supported(q, k, v) -> bool:
+    """q [n, H, D], k [l, H, D], v [l, H | 1, D]: tensors of one dtype on the GPU, contiguous in the last dimension, in a
+    shape the library accepts, with at least one query and one key, and a kernel table that has the entries."""
+    return _supported(q, k, v, "pair_sigmoid")
+
+
 def use_kernels(q, k, v) -> bool:
     """supported(q, k, v) under the switch SGF_PAIR_ATTN (read on every call)."""
-    s = os.environ.get("SGF_PAIR_ATTN")
-    if s is not None and not _switch("SGF_PAIR_ATTN", True):
-        return False
-    if not supported(q, k, v):
-        return False
-    return s is not None or q.shape[0] * k.shape[0] * q.shape[1] >= (PAIR_MIN_PAIRS_BF16 if q.dtype == _BF16 else PAIR_MIN_PAIRS)
+    return _use(q, k, v, "pair_sigmoid")
+
+
+def softmax_supported(q, k, v) -> bool:
+    """supported() for the softmax kernels: the same operand rules, and a kernel table that has the pair_softmax_* entries."""
+    return _supported(q, k, v, "pair_softmax")
+
+
+def use_softmax_kernels(q, k, v) -> bool:
+    """softmax_supported(q, k, v) under the switch SGF_PAIR_SOFTMAX (read on every call): 0 = always the dense path, 1 = the
+    kernels wherever supported, unset = the kernels from SOFTMAX_MIN_PAIRS / SOFTMAX_MIN_PAIRS_BF16 score entries upward."""
+    return _use(q, k, v, "pair_softmax")
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
@@ -183,100 +207,74 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
+# ------------------------------------------------------------------------------------------------
+# autograd: one implementation; `scale` is () for the sigmoid function and (scale,) for the softmax function, and goes to the
+# table's methods where their signatures have it (the methods are looked up on the table at call time)
+# ------------------------------------------------------------------------------------------------
+def _forward(ctx, family: str, q, k, v, *scale):
+    ops.K.check(q, k, v)
+    t = _table(family + "_fwd")
+    q, k, v = _rows(q), _rows(k), _rows(v)
+    out, saved = getattr(t, family + "_fwd")(q, k, v, *scale)
+    ctx.save_for_backward(q, k, v, out, saved)       # saved: the fp32 row sums (sigmoid) / log-sum-exp (softmax) [n, H]
+    ctx.table, ctx.family, ctx.scale = t, family, scale
+    return out
+
+
+def _backward(ctx, g):
+    """one gradient per input of the function: dq, dk, dv and, for the softmax function, None for the scale"""
+    t, family, scale = ctx.table, ctx.family, ctx.scale
+    if torch.is_grad_enabled():          # (only under create_graph=True)
+        name, switch = _ARMS[family][:2]
+        raise RuntimeError(f"sgformer_amd: pair_attn.{name} is once differentiable; backward with "
+                           f"create_graph=True is not implemented ({switch}=0 keeps the twice differentiable path)")
+    q, k, v, out, saved = ctx.saved_tensors
+    need_q, need_k, need_v = ctx.needs_input_grad[:3]
+    none = (None,) * len(scale)
+    if not (need_q or need_k or need_v):
+        return (None, None, None) + none
+    g = _rows(g if g.dtype == q.dtype else g.to(q.dtype))
+    dq, delta = getattr(t, family + "_bwd_q")(g, out, saved, q, k, v, *scale, want_dq=need_q)      # (delta is bwd_kv's operand too)
+    dk = dv = None
+    if need_k or need_v:
+        dk, dv = getattr(t, family + "_bwd_kv")(g, saved, delta, q, k, v, *scale)
+    return (dq, (dk if need_k else None), (dv if need_v else None)) + none
+
+
 class _SigmoidAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v):
-        ops.K.check(q, k, v)
-        t = _table()
-        q, k, v = _rows(q), _rows(k), _rows(v)
-        out, rowsum = t.pair_sigmoid_fwd(q, k, v)
-        ctx.save_for_backward(q, k, v, out, rowsum)
-        ctx.table = t
-        return out
+        return _forward(ctx, "pair_sigmoid", q, k, v)
 
-    @staticmethod
-    def backward(ctx, g):
-        if torch.is_grad_enabled():          # (only under create_graph=True)
-            raise RuntimeError("sgformer_amd: pair_attn.sigmoid_attention is once differentiable; backward with "
-                               "create_graph=True is not implemented (SGF_PAIR_ATTN=0 keeps the twice differentiable path)")
-        q, k, v, out, rowsum = ctx.saved_tensors
-        t = ctx.table
-        need_q, need_k, need_v = ctx.needs_input_grad
-        if not (need_q or need_k or need_v):
-            return None, None, None
-        g = _rows(g if g.dtype == q.dtype else g.to(q.dtype))
-        dq, delta = t.pair_sigmoid_bwd_q(g, out, rowsum, q, k, v, want_dq=need_q)      # (delta is bwd_kv's operand too)
-        dk = dv = None
-        if need_k or need_v:
-            dk, dv = t.pair_sigmoid_bwd_kv(g, rowsum, delta, q, k, v)
-        return dq, (dk if need_k else None), (dv if need_v else None)
-
-
-def sigmoid_attention(q, k, v) -> torch.Tensor:
-    """out [n, H, D] of the sigmoid kernel for q [n, H, D], k [l, H, D], v [l, H | 1, D]; differentiable once in q, k and v.
-    The caller asks supported() / use_kernels() first: an unsupported call is an error here, not a fallback."""
-    if not supported(q, k, v):
-        raise RuntimeError(f"pair_attn.sigmoid_attention: unsupported operands q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)}, "
-                           f"v {tuple(v.shape)} (D in {{32, 64, 128}}, H <= 8, float32 or bfloat16, one device)")
-    return _SigmoidAttention.apply(q, k, v)
-
-
-# ------------------------------------------------------------------------------------------------
-# the exact softmax attention
-# ------------------------------------------------------------------------------------------------
-def softmax_supported(q, k, v) -> bool:
-    """supported() for the softmax kernels: the same operand rules, and a kernel table that has the pair_softmax_* entries."""
-    return _supported(q, k, v, "pair_softmax")
-
-
-def use_softmax_kernels(q, k, v) -> bool:
-    """softmax_supported(q, k, v) under the switch SGF_PAIR_SOFTMAX (read on every call): 0 = always the dense path, 1 = the
-    kernels wherever supported, unset = the kernels from SOFTMAX_MIN_PAIRS / SOFTMAX_MIN_PAIRS_BF16 score entries upward."""
-    s = os.environ.get("SGF_PAIR_SOFTMAX")
-    if s is not None and not _switch("SGF_PAIR_SOFTMAX", True):
-        return False
-    if not softmax_supported(q, k, v):
-        return False
-    return s is not None or q.shape[0] * k.shape[0] * q.shape[1] >= (SOFTMAX_MIN_PAIRS_BF16 if q.dtype == _BF16
-                                                                      else SOFTMAX_MIN_PAIRS)
+    backward = staticmethod(_backward)
 
 
 class _SoftmaxAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
-        ops.K.check(q, k, v)
-        t = _table("pair_softmax_fwd")
-        q, k, v = _rows(q), _rows(k), _rows(v)
-        out, lse = t.pair_softmax_fwd(q, k, v, scale)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.table, ctx.scale = t, scale
-        return out
+        return _forward(ctx, "pair_softmax", q, k, v, scale)
 
-    @staticmethod
-    def backward(ctx, g):
-        if torch.is_grad_enabled():          # (only under create_graph=True)
-            raise RuntimeError("sgformer_amd: pair_attn.softmax_attention is once differentiable; backward with "
-                               "create_graph=True is not implemented (SGF_PAIR_SOFTMAX=0 keeps the twice differentiable path)")
-        q, k, v, out, lse = ctx.saved_tensors
-        t, scale = ctx.table, ctx.scale
-        need_q, need_k, need_v = ctx.needs_input_grad[:3]
-        if not (need_q or need_k or need_v):
-            return None, None, None, None
-        g = _rows(g if g.dtype == q.dtype else g.to(q.dtype))
-        dq, delta = t.pair_softmax_bwd_q(g, out, lse, q, k, v, scale, want_dq=need_q)      # (delta is bwd_kv's operand too)
-        dk = dv = None
-        if need_k or need_v:
-            dk, dv = t.pair_softmax_bwd_kv(g, lse, delta, q, k, v, scale)
-        return dq, (dk if need_k else None), (dv if need_v else None), None
+    backward = staticmethod(_backward)
+
+
+def _require(q, k, v, family: str) -> None:
+    if not _supported(q, k, v, family):
+        raise RuntimeError(f"pair_attn.{_ARMS[family][0]}: unsupported operands q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)}, "
+                           f"v {tuple(v.shape)} (D in {{32, 64, 128}}, H <= 8, float32 or bfloat16, one device)")
+
+
+def sigmoid_attention(q, k, v) -> torch.Tensor:
+    """out [n, H, D] of the sigmoid kernel for q [n, H, D], k [l, H, D], v [l, H | 1, D]; differentiable once in q, k and v.
+    The caller asks supported() / use_kernels() first: an unsupported call is an error here, not a fallback."""
+    _require(q, k, v, "pair_sigmoid")
+    return _SigmoidAttention.apply(q, k, v)
 
 
 def softmax_attention(q, k, v, scale: float = 1.0) -> torch.Tensor:
     """out [n, H, D] = softmax over the keys of scale q . k, times v, for q [n, H, D], k [l, H, D], v [l, H | 1, D];
     differentiable once in q, k and v (scale is a constant: a finite, positive float).  The caller asks softmax_supported() /
     use_softmax_kernels() first: an unsupported call is an error here, not a fallback."""
-    if not softmax_supported(q, k, v):
-        raise RuntimeError(f"pair_attn.softmax_attention: unsupported operands q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)}, "
-                           f"v {tuple(v.shape)} (D in {{32, 64, 128}}, H <= 8, float32 or bfloat16, one device)")
+    _require(q, k, v, "pair_softmax")
     scale = float(scale)
     if not (0.0 < scale < float("inf")):
         raise ValueError(f"pair_attn.softmax_attention: scale must be finite and positive, got {scale}")
