@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 668 /* 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 669 /* 0.6.15: sgf_pair_sigmoid_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv and sgf_pair_softmax_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv, the all-pair attention kernels for SGF_F32_BF16X3 (csrc/pair_attn.hip); 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -41,6 +41,7 @@ extern "C" {
  * torch.set_float32_matmul_precision('high') ("each float32 number as the sum of two bfloat16 numbers").  Per product the
  * error is at most 3 * 2^-16 |a b|; an inf / NaN input gives a non-finite output wherever SGF_F32 would.  Accepted only
  * by the entries that say so and by their *_supported queries (same shapes as SGF_F32); every other entry rejects it.
+ * The all-pair attention (N7, N8) takes it through entries of its own, sgf_pair_*_x3_* (N9), which accept nothing else.
  * Where `dtype` names an output's storage (sgf_combine_fc_bwd: dx1 / dx2), SGF_F32_BF16X3 means fp32 outputs. */
 #define SGF_F32_BF16X3 2
 
@@ -1132,7 +1133,7 @@ int sgf_head_rows_bwd(const void* x1, int64_t ld1, float a, const void* x2, int6
  * [l, heads * d], v / dv [l, v_heads * d] with v_heads == heads, or v_heads == 1 for one value head that every head shares
  * (dv is then the sum over the heads, formed inside the kernel in head order); rowsum fp32 [n, heads] (= r).
  * Shapes (sgf_pair_sigmoid_supported): d in {32, 64, 128}, 1 <= heads <= 8, SGF_F32 or SGF_BF16; anything else, and
- * SGF_F32_BF16X3, is SGF_E_UNSUPPORTED (fp32 tensors run the exact kernel under every matmul-precision setting).  n and l
+ * SGF_F32_BF16X3, is SGF_E_UNSUPPORTED (the split-bf16 products have entries of their own: N9).  n and l
  * are arbitrary (< 2^31); a key past l adds exactly 0 (it is masked, not zero-filled: sigmoid(0) = 0.5), rows past n are
  * never stored.  z >= 17 gives S = 1, z <= -104 gives S = 0, and 1 - S is formed from S: a saturated pair has an exactly
  * zero dZ.  No NaN comes out of the exponential's overflow.
@@ -1178,7 +1179,7 @@ int sgf_pair_sigmoid_bwd_kv(const void* g, int64_t ldg, const float* rowsum, con
  *     dv_j = sum_i P g_i                                                 dk_j = sum_i dZ q_i   (sgf_pair_softmax_bwd_kv)
  * Operands, layouts, leading dimensions, the 16-byte row alignment, v_heads in {heads, 1} (dv summed over the heads inside
  * the kernel, in head order), the shapes (sgf_pair_softmax_supported: d in {32, 64, 128}, 1 <= heads <= 8, SGF_F32 or
- * SGF_BF16; SGF_F32_BF16X3 is SGF_E_UNSUPPORTED), the workspace (delta fp32 [n, heads], written by bwd_q — dq == NULL:
+ * SGF_BF16; SGF_F32_BF16X3 is SGF_E_UNSUPPORTED here: N9), the workspace (delta fp32 [n, heads], written by bwd_q — dq == NULL:
  * delta only — and read by bwd_kv), the checks and their order, and sgf_pair_softmax_lap_rows are those of N7.  The
  * differences: `lse` fp32 [n, heads] stands where `rowsum` stood, and `scale` (after dtype) multiplies the scores; it must
  * be finite and positive, else SGF_E_INVALID (checked after the shape, before the pointers and for an empty problem too).
@@ -1210,6 +1211,52 @@ int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* lse, const 
                             int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
                             int32_t d, int32_t dtype, float scale, void* dk, int64_t lddk, void* dv, int64_t lddv,
                             const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N9 — N7 and N8 for SGF_F32_BF16X3: fp32 storage, every matrix product (z, g . v, S V / P V, dZ K, dZ Q, W g) formed as
+ * three bf16 matrix-core products.  Two families of five entries; each entry has the argument list of its N7 / N8
+ * counterpart, `dtype` included, and computes the same formulas.  `dtype` must be SGF_F32_BF16X3: SGF_F32, SGF_BF16 and
+ * anything else are SGF_E_UNSUPPORTED here, exactly as the N7 / N8 entries reject SGF_F32_BF16X3.  Shapes
+ * (sgf_pair_*_x3_supported): d in {32, 64, 128}, 1 <= heads <= 8, v_heads in {1, heads}.  Pointers, leading dimensions,
+ * the 16-byte row alignment (4 fp32), the checks and their order, and the workspace (sgf_pair_sigmoid_workspace_bytes /
+ * sgf_pair_softmax_workspace_bytes: delta fp32 [n, heads]) are those of SGF_F32 in N7 / N8.
+ *   While a swept tile is staged into LDS every element is split once, hi = bf16(a), lo = bf16(a - hi) (round to nearest
+ *   even, lo = 0 where hi is not finite), into two bf16 images in the SGF_BF16 layouts; the resident rows are split the same
+ *   way into two fragment sets, and the fp32 score tile (S, P, dZ, S / r) is split in registers as it becomes the operand
+ *   of the second product.  Each product is hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_bf16 into one fp32 accumulator:
+ *   at most 3 * 2^-16 |a| |b| per product.  Operands that bf16 holds exactly give the products of SGF_F32.
+ *   expf, the online maximum and rescale, lse, delta = g . out, the row sums and the denominators are the fp32 code of
+ *   SGF_F32; the sums are over the unrounded weights (out is divided by r itself, not by a sum of rounded weights as under
+ *   SGF_BF16).  A score error dz moves a softmax weight by the factor exp(dz): |dz| <= 2^-14 scale |q| . |k|.
+ * Fixed-order sums inside one workgroup, no atomics: bit-reproducible.  sgf_pair_*_x3_lap_rows: as in N7 (0: one resident
+ * tile per workgroup), for dtype SGF_F32_BF16X3 only.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_pair_sigmoid_x3_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype);
+int64_t sgf_pair_sigmoid_x3_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps);
+int sgf_pair_sigmoid_x3_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n,
+                            int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* out, int64_t ldo,
+                            float* rowsum, void* stream);
+int sgf_pair_sigmoid_x3_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* rowsum, const void* q,
+                              int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                              int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dq, int64_t lddq, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int sgf_pair_sigmoid_x3_bwd_kv(const void* g, int64_t ldg, const float* rowsum, const void* q, int64_t ldq, const void* k,
+                               int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
+                               int32_t d, int32_t dtype, void* dk, int64_t lddk, void* dv, int64_t lddv, const void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t sgf_pair_softmax_x3_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype);
+int64_t sgf_pair_softmax_x3_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps);
+int sgf_pair_softmax_x3_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n,
+                            int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* out,
+                            int64_t ldo, float* lse, void* stream);
+int sgf_pair_softmax_x3_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* lse, const void* q,
+                              int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                              int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* dq, int64_t lddq,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int sgf_pair_softmax_x3_bwd_kv(const void* g, int64_t ldg, const float* lse, const void* q, int64_t ldq, const void* k,
+                               int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
+                               int32_t d, int32_t dtype, float scale, void* dk, int64_t lddk, void* dv, int64_t lddv,
+                               const void* workspace, size_t workspace_bytes, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

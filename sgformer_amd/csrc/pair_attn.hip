@@ -22,6 +22,10 @@
 //   * fp32 storage: v_mfma_f32_32x32x2_f32 (exact fp32 products, one operand register per lane): register q of X is the B
 //     operand of one MFMA whose two k are X's rows of the two lane halves; the A operand is a 4-byte read of the
 //     row-major image, so one image serves both products.  S and dZ are used unrounded.
+//   * fp32 storage under SGF_F32_BF16X3 (the sgf_pair_*_x3_* entries, block N9; arm tag f32x3): the bf16 arm's MFMA, layouts and
+//     swap23 order on operands split as a = hi + lo in bf16, three products per product into one fp32 accumulator; the swept
+//     tile is split once as it is staged (two bf16 planes per image), the resident rows once into two fragment sets, X as it
+//     becomes the B operand.  expf, maxima, row sums, lse and delta are the fp32 arm's; the sums are over the unrounded weights.
 //   * sigmoid: u = exp(-z), S = 1 / (1 + u) in fp32.  z >= 17: 1 + u rounds to 1, S = 1.  z <= -88.8: u = inf, S = 0 (no
 //     NaN: nothing is multiplied by u).  1 - S is formed from S, so a saturated score has an exactly zero derivative.
 //   * tails: a swept row past the end is staged as zeros AND masked (a zero key would score sigmoid(0) = 0.5): keys by a
@@ -70,34 +74,81 @@ __device__ __forceinline__ float sigmoid(float z) {
   return __builtin_amdgcn_rcpf(1.0f + u);
 }
 
-// One swept tile of SW rows x D features in LDS: `rm` row-major (pitch D + pad), `tr` transposed [feature][row] (bf16 only).
-template <typename T, int D, int SW>
+// The arm of a kernel: its storage type (uint16_t: bf16, float: fp32 with exact fp32 products), or f32x3: fp32 storage whose
+// matrix products are three bf16 matrix-core products (SGF_F32_BF16X3; the comment in front of PaImg's f32x3 members).
+struct f32x3 {};
+template <typename A>
+struct pa_elem { using type = A; };
+template <>
+struct pa_elem<f32x3> { using type = float; };
+
+// the resident row's fragments of the f32x3 arm: the two bf16 terms of a = hi + lo
+struct PaSplitFrag {
+  bf16x8 hi, lo;
+};
+
+// One swept tile of SW rows x D features in LDS: `rm` row-major (pitch D + pad), `tr` transposed [feature][row] (bf16 and
+// f32x3).
+//
+// f32x3: every fp32 element is split once while the tile is staged, hi = bf16_rne(a), lo = bf16_rne(a - hi), lo = 0 where hi
+// is not finite (common.h split_bf16x2), into two bf16 images (the `hi` plane, then the `lo` plane) in the bf16 arm's
+// layouts; the resident rows are split the same way into two fragment sets, and the accumulator tile of the second products
+// (S, P, dZ, W: fp32 in registers) is split as it becomes the B operand.  Every product is hi.hi + hi.lo + lo.hi on
+// v_mfma_f32_32x32x16_bf16 into one fp32 accumulator: the dropped lo.lo term is below 2^-16 of |a| |b|.  Everything that
+// is not a matrix product (exp, maxima, row sums, lse, delta) is the fp32 arm's code.
+template <typename A, int D, int SW>
 struct PaImg {
-  static constexpr bool kBf16 = std::is_same<T, uint16_t>::value;
+  using T = typename pa_elem<A>::type;               // storage
+  static constexpr bool kBf16 = std::is_same<A, uint16_t>::value;
+  static constexpr bool kX3 = std::is_same<A, f32x3>::value;
+  static constexpr bool kTrans = kBf16 || kX3;       // bf16 matrix cores: the second products read the transposed image
+  using L = typename std::conditional<kTrans, uint16_t, float>::type;   // LDS element
   static constexpr int kVec = 16 / static_cast<int>(sizeof(T));
-  static constexpr int kPitch = D + (kBf16 ? 8 : 4);
+  static constexpr int kPitch = D + (kTrans ? 8 : 4);
   static constexpr int kPitchT = SW + 8;
-  static constexpr int kRm = SW * kPitch;
-  static constexpr int kTr = kBf16 ? D * kPitchT : 4;
-  static constexpr int kFrags = kBf16 ? D / 16 : D / 2;
-  using Frag = typename std::conditional<kBf16, bf16x8, float>::type;
+  static constexpr int kRmPlane = SW * kPitch;
+  static constexpr int kTrPlane = D * kPitchT;
+  static constexpr int kRm = (kX3 ? 2 : 1) * kRmPlane;
+  static constexpr int kTr = kTrans ? (kX3 ? 2 : 1) * kTrPlane : 4;
+  static constexpr int kFrags = kTrans ? D / 16 : D / 2;
+  using Frag = typename std::conditional<kX3, PaSplitFrag, typename std::conditional<kBf16, bf16x8, float>::type>::type;
 
   // rows row0 .. row0 + SW - 1 of src (already at the head's first column); rows >= nrows are zeros
   template <bool RM, bool TR>
-  static __device__ __forceinline__ void stage(const T* __restrict__ src, int64_t ld, int64_t row0, int64_t nrows, T* rm,
-                                               T* tr) {
+  static __device__ __forceinline__ void stage(const T* __restrict__ src, int64_t ld, int64_t row0, int64_t nrows, L* rm,
+                                               L* tr) {
     constexpr int CH = D / kVec;
     for (int idx = threadIdx.x; idx < SW * CH; idx += kPaThreads) {
       const int row = idx % SW, c = idx / SW;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (row0 + row < nrows) v = *reinterpret_cast<const uint4*>(src + (row0 + row) * ld + kVec * c);
-      if constexpr (RM) *reinterpret_cast<uint4*>(rm + row * kPitch + kVec * c) = v;
-      if constexpr (TR && kBf16) {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      if constexpr (kX3) {
+        uint2 h, l;
+        split_bf16x2(__uint_as_float(v.x), __uint_as_float(v.y), h.x, l.x);
+        split_bf16x2(__uint_as_float(v.z), __uint_as_float(v.w), h.y, l.y);
+        if constexpr (RM) {
+          *reinterpret_cast<uint2*>(rm + row * kPitch + 4 * c) = h;
+          *reinterpret_cast<uint2*>(rm + kRmPlane + row * kPitch + 4 * c) = l;
+        }
+        if constexpr (TR) {
+          const uint32_t wh[2] = {h.x, h.y}, wl[2] = {l.x, l.y};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          tr[(8 * c + 2 * e) * kPitchT + row] = static_cast<T>(w[e] & 0xffffu);
-          tr[(8 * c + 2 * e + 1) * kPitchT + row] = static_cast<T>(w[e] >> 16);
+          for (int e = 0; e < 2; ++e) {
+            tr[(4 * c + 2 * e) * kPitchT + row] = static_cast<L>(wh[e] & 0xffffu);
+            tr[(4 * c + 2 * e + 1) * kPitchT + row] = static_cast<L>(wh[e] >> 16);
+            tr[kTrPlane + (4 * c + 2 * e) * kPitchT + row] = static_cast<L>(wl[e] & 0xffffu);
+            tr[kTrPlane + (4 * c + 2 * e + 1) * kPitchT + row] = static_cast<L>(wl[e] >> 16);
+          }
+        }
+      } else {
+        if constexpr (RM) *reinterpret_cast<uint4*>(rm + row * kPitch + kVec * c) = v;
+        if constexpr (TR && kBf16) {
+          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            tr[(8 * c + 2 * e) * kPitchT + row] = static_cast<T>(w[e] & 0xffffu);
+            tr[(8 * c + 2 * e + 1) * kPitchT + row] = static_cast<T>(w[e] >> 16);
+          }
         }
       }
     }
@@ -105,7 +156,23 @@ struct PaImg {
 
   // the resident row's fragments (B operand of the first products): row points at the head's first column of that row
   static __device__ __forceinline__ void load_frags(const T* __restrict__ row, int hh, Frag* f) {
-    if constexpr (kBf16) {
+    if constexpr (kX3) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) {
+        const float4 a = *reinterpret_cast<const float4*>(row + 16 * s + 8 * hh);
+        const float4 b = *reinterpret_cast<const float4*>(row + 16 * s + 8 * hh + 4);
+        union {
+          bf16x8 v;
+          uint32_t u[4];
+        } h, l;
+        split_bf16x2(a.x, a.y, h.u[0], l.u[0]);
+        split_bf16x2(a.z, a.w, h.u[1], l.u[1]);
+        split_bf16x2(b.x, b.y, h.u[2], l.u[2]);
+        split_bf16x2(b.z, b.w, h.u[3], l.u[3]);
+        f[s].hi = h.v;
+        f[s].lo = l.v;
+      }
+    } else if constexpr (kBf16) {
 #pragma unroll
       for (int s = 0; s < kFrags; ++s) f[s] = *reinterpret_cast<const bf16x8*>(row + 16 * s + 8 * hh);
     } else {
@@ -114,10 +181,17 @@ struct PaImg {
     }
   }
 
-  // this lane's share of frags . row (the other lane half holds the rest)
-  static __device__ __forceinline__ float dot_frags(const Frag* f, const T* __restrict__ row, int hh) {
+  // this lane's share of frags . row (the other lane half holds the rest); `frow`: the row the fragments were loaded from
+  // (f32x3 reads it again: the dot is taken from the unsplit fp32 values)
+  static __device__ __forceinline__ float dot_frags(const Frag* f, const T* __restrict__ frow, const T* __restrict__ row,
+                                                    int hh) {
     float acc = 0.f;
-    if constexpr (kBf16) {
+    if constexpr (kX3) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc = fmaf(frow[16 * s + 8 * hh + j], row[16 * s + 8 * hh + j], acc);
+    } else if constexpr (kBf16) {
 #pragma unroll
       for (int s = 0; s < kFrags; ++s) {
         const bf16x8 o = *reinterpret_cast<const bf16x8*>(row + 16 * s + 8 * hh);
@@ -133,12 +207,21 @@ struct PaImg {
   }
 
   // X[swept row][resident row] = sum over the features, sub-tile st: lane r reads LDS row swap23(r)
-  static __device__ __forceinline__ f32x16 dot(const T* rm, int st, int r, int hh, const Frag* b) {
+  static __device__ __forceinline__ f32x16 dot(const L* rm, int st, int r, int hh, const Frag* b) {
     f32x16 acc;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    const T* a = rm + (32 * st + swap23(r)) * kPitch + (kBf16 ? 8 * hh : hh);
-    if constexpr (kBf16) {
+    const L* a = rm + (32 * st + swap23(r)) * kPitch + (kTrans ? 8 * hh : hh);
+    if constexpr (kX3) {
+#pragma unroll
+      for (int s = 0; s < kFrags; ++s) {
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a + 16 * s);
+        const bf16x8 al = *reinterpret_cast<const bf16x8*>(a + kRmPlane + 16 * s);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b[s].hi, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, b[s].lo, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b[s].hi, acc, 0, 0, 0);
+      }
+    } else if constexpr (kBf16) {
 #pragma unroll
       for (int s = 0; s < kFrags; ++s)
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(a + 16 * s), b[s], acc, 0, 0, 0);
@@ -150,8 +233,28 @@ struct PaImg {
   }
 
   // out[t][feature 32 t + .][resident row] += sum over the swept rows of image[row][feature] x[row][resident row]
-  static __device__ __forceinline__ void acc(const T* rm, const T* tr, int st, const f32x16& x, f32x16* out, int r, int hh) {
-    if constexpr (kBf16) {
+  static __device__ __forceinline__ void acc(const L* rm, const L* tr, int st, const f32x16& x, f32x16* out, int r, int hh) {
+    if constexpr (kX3) {
+      union {
+        bf16x8 v;
+        uint32_t u[4];
+      } xh[2], xl[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) split_bf16x2(x[8 * s + 2 * i], x[8 * s + 2 * i + 1], xh[s].u[i], xl[s].u[i]);
+#pragma unroll
+      for (int t = 0; t < D / 32; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const L* a = tr + (32 * t + r) * kPitchT + 32 * st + 16 * s + 8 * hh;
+          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a);
+          const bf16x8 al = *reinterpret_cast<const bf16x8*>(a + kTrPlane);
+          out[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[s].v, out[t], 0, 0, 0);
+          out[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[s].v, out[t], 0, 0, 0);
+          out[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[s].v, out[t], 0, 0, 0);
+        }
+    } else if constexpr (kBf16) {
       union {
         bf16x8 v;
         uint32_t u[4];
@@ -191,17 +294,23 @@ struct PaImg {
   }
 };
 
-// swept rows per stage: two sub-tiles where the LDS images stay below 64 KiB
-template <typename T, int WHICH>
-constexpr int pa_sweep() { return std::is_same<T, uint16_t>::value && WHICH != 2 ? 64 : 32; }
+// swept rows per stage: two sub-tiles where the LDS images stay below 64 KiB (f32x3 holds two planes per image: two
+// sub-tiles up to D = 64)
+template <typename A, int WHICH, int D>
+constexpr int pa_sweep() {
+  if (WHICH == 2) return 32;
+  return std::is_same<A, uint16_t>::value || (std::is_same<A, f32x3>::value && D <= 64) ? 64 : 32;
+}
 
-template <typename T, int D>
+template <typename A, int D>
 __global__ __launch_bounds__(kPaThreads) void k_pa_fwd(const PaArgs p) {
-  constexpr int SW = pa_sweep<T, 0>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
-  __shared__ __attribute__((aligned(16))) T vs[I::kBf16 ? 4 : I::kRm];
-  __shared__ __attribute__((aligned(16))) T vt[I::kTr];
+  constexpr int SW = pa_sweep<A, 0, D>();
+  using I = PaImg<A, D, SW>;
+  using T = typename I::T;
+  using L = typename I::L;
+  __shared__ __attribute__((aligned(16))) L ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) L vs[I::kTrans ? 4 : I::kRm];
+  __shared__ __attribute__((aligned(16))) L vt[I::kTr];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
@@ -218,7 +327,7 @@ __global__ __launch_bounds__(kPaThreads) void k_pa_fwd(const PaArgs p) {
   float rs = 0.f, den = 0.f;
   for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
     I::template stage<true, false>(kp, p.ldk, j0, p.l, ks, nullptr);
-    I::template stage<!I::kBf16, true>(vp, p.ldv, j0, p.l, vs, vt);
+    I::template stage<!I::kTrans, true>(vp, p.ldv, j0, p.l, vs, vt);
     __syncthreads();
 #pragma unroll
     for (int st = 0; st < SW / 32; ++st) {
@@ -275,14 +384,16 @@ __device__ __forceinline__ float pa_exp(float t) {
 }
 
 // D = 128: m, the held score tiles and the rescale put the unbounded allocation at 261 (bf16) / 283 (fp32) registers, one
-// wave per SIMD where the sigmoid forward runs two; asked for two waves the compiler fits 206 / 210 without a spill.
-template <typename T, int D>
+// wave per SIMD where the sigmoid forward runs two; asked for two waves the compiler fits 206 / 210 without a spill (f32x3: 243).
+template <typename A, int D>
 __global__ __launch_bounds__(kPaThreads, D == 128 ? 2 : 1) void k_ps_fwd(const PaArgs p, const float scale) {
-  constexpr int SW = pa_sweep<T, 0>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
-  __shared__ __attribute__((aligned(16))) T vs[I::kBf16 ? 4 : I::kRm];
-  __shared__ __attribute__((aligned(16))) T vt[I::kTr];
+  constexpr int SW = pa_sweep<A, 0, D>();
+  using I = PaImg<A, D, SW>;
+  using T = typename I::T;
+  using L = typename I::L;
+  __shared__ __attribute__((aligned(16))) L ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) L vs[I::kTrans ? 4 : I::kRm];
+  __shared__ __attribute__((aligned(16))) L vt[I::kTr];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
@@ -299,7 +410,7 @@ __global__ __launch_bounds__(kPaThreads, D == 128 ? 2 : 1) void k_ps_fwd(const P
   float m = -INFINITY, rs = 0.f, den = 0.f;
   for (int64_t j0 = 0; j0 < p.l; j0 += SW) {
     I::template stage<true, false>(kp, p.ldk, j0, p.l, ks, nullptr);
-    I::template stage<!I::kBf16, true>(vp, p.ldv, j0, p.l, vs, vt);
+    I::template stage<!I::kTrans, true>(vp, p.ldv, j0, p.l, vs, vt);
     __syncthreads();
     f32x16 x[SW / 32];
     float tm = -INFINITY;
@@ -381,13 +492,15 @@ struct SoftmaxScore {
   }
 };
 
-template <typename T, int D, typename Score>
+template <typename A, int D, typename Score>
 __global__ __launch_bounds__(kPaThreads) void k_pair_bwd_q(const PaArgs p, const float scale) {
-  constexpr int SW = pa_sweep<T, 1>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T ks[I::kRm];
-  __shared__ __attribute__((aligned(16))) T vs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T kt[I::kTr];
+  constexpr int SW = pa_sweep<A, 1, D>();
+  using I = PaImg<A, D, SW>;
+  using T = typename I::T;
+  using L = typename I::L;
+  __shared__ __attribute__((aligned(16))) L ks[I::kRm];
+  __shared__ __attribute__((aligned(16))) L vs[I::kRm];
+  __shared__ __attribute__((aligned(16))) L kt[I::kTr];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int h = blockIdx.y, hv = p.v_heads == 1 ? 0 : h;
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kPaRows + 32 * wid + r;
@@ -396,7 +509,8 @@ __global__ __launch_bounds__(kPaThreads) void k_pair_bwd_q(const PaArgs p, const
   const T* vp = static_cast<const T*>(p.v) + hv * D;
   typename I::Frag qf[I::kFrags], gf[I::kFrags];
   I::load_frags(static_cast<const T*>(p.g) + ic * p.ldg + h * D, hh, gf);
-  float delta = I::dot_frags(gf, static_cast<const T*>(p.o) + ic * p.ldo + h * D, hh);
+  const T* grow = static_cast<const T*>(p.g) + ic * p.ldg + h * D;
+  float delta = I::dot_frags(gf, grow, static_cast<const T*>(p.o) + ic * p.ldo + h * D, hh);
   delta += __shfl_xor(delta, 32, 64);
   if (i < p.n && hh == 0) p.delta[i * p.heads + h] = delta;
   if (!p.dq) return;                                 // (uniform: delta only)
@@ -431,14 +545,16 @@ __global__ __launch_bounds__(kPaThreads) void k_pair_bwd_q(const PaArgs p, const
   if (i < p.n) I::template store<false>(static_cast<T*>(p.dq) + i * p.lddq + h * D, dq, hh, 1.f);
 }
 
-template <typename T, int D, typename Score>
+template <typename A, int D, typename Score>
 __global__ __launch_bounds__(kPaThreads) void k_pair_bwd_kv(const PaArgs p, const float scale) {
-  constexpr int SW = pa_sweep<T, 2>();
-  using I = PaImg<T, D, SW>;
-  __shared__ __attribute__((aligned(16))) T qs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T gs[I::kRm];
-  __shared__ __attribute__((aligned(16))) T qt[I::kTr];
-  __shared__ __attribute__((aligned(16))) T gt[I::kTr];
+  constexpr int SW = pa_sweep<A, 2, D>();
+  using I = PaImg<A, D, SW>;
+  using T = typename I::T;
+  using L = typename I::L;
+  __shared__ __attribute__((aligned(16))) L qs[I::kRm];
+  __shared__ __attribute__((aligned(16))) L gs[I::kRm];
+  __shared__ __attribute__((aligned(16))) L qt[I::kTr];
+  __shared__ __attribute__((aligned(16))) L gt[I::kTr];
   __shared__ float rc_s[SW], delta_s[SW];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const bool shared_v = p.v_heads != p.heads;        // one value head: this workgroup walks every head, dv sums over them
@@ -498,8 +614,9 @@ __global__ __launch_bounds__(kPaThreads) void k_pair_bwd_kv(const PaArgs p, cons
   if (shared_v && j < p.l) I::template store<false>(static_cast<T*>(p.dv) + j * p.lddv, dv, hh, 1.f);
 }
 
-inline bool pa_shape_ok(int heads, int v_heads, int d, int dtype) {
-  if (dtype != SGF_F32 && dtype != SGF_BF16) return false;
+// x3: the sgf_pair_*_x3_* families, which take SGF_F32_BF16X3 and nothing else (the exact families never take it)
+inline bool pa_shape_ok(int heads, int v_heads, int d, int dtype, bool x3 = false) {
+  if (x3 ? dtype != SGF_F32_BF16X3 : (dtype != SGF_F32 && dtype != SGF_BF16)) return false;
   if (d != 32 && d != 64 && d != 128) return false;
   return heads >= 1 && heads <= 8 && (v_heads == 1 || v_heads == heads);
 }
@@ -507,13 +624,13 @@ inline bool pa_shape_ok(int heads, int v_heads, int d, int dtype) {
 inline bool pa_aligned(const void* p, int64_t ld, int64_t per16) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % per16 == 0; }
 
 // sizes, head counts, width and dtype of all three launches
-int check_pa(const char* fn, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype) {
+int check_pa(const char* fn, bool x3, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype) {
   SGF_REQUIRE(n >= 0 && l >= 0, SGF_E_INVALID, "%s: negative size n=%lld l=%lld", fn, static_cast<long long>(n),
               static_cast<long long>(l));
   SGF_REQUIRE(v_heads == 1 || v_heads == heads, SGF_E_INVALID, "%s: v_heads=%d must be 1 or heads=%d", fn, v_heads, heads);
-  SGF_REQUIRE(pa_shape_ok(heads, v_heads, d, dtype), SGF_E_UNSUPPORTED,
-              "%s: needs d in {32, 64, 128}, 1 <= heads <= 8 and SGF_F32 or SGF_BF16 (heads=%d, d=%d, dtype %d)", fn, heads, d,
-              dtype);
+  SGF_REQUIRE(pa_shape_ok(heads, v_heads, d, dtype, x3), SGF_E_UNSUPPORTED,
+              "%s: needs d in {32, 64, 128}, 1 <= heads <= 8 and %s (heads=%d, d=%d, dtype %d)", fn,
+              x3 ? "SGF_F32_BF16X3" : "SGF_F32 or SGF_BF16", heads, d, dtype);
   SGF_REQUIRE(n < (static_cast<int64_t>(1) << 31) && l < (static_cast<int64_t>(1) << 31), SGF_E_UNSUPPORTED,
               "%s: more than 2^31 - 1 rows", fn);
   return SGF_OK;
@@ -539,34 +656,39 @@ int check_pa_rows(const char* fn, const PaOperand* ops, int count, int dtype) {
   return SGF_OK;
 }
 
-// The two arms of the entries: what the forward saves per row, and what l == 0 would ask for.
+// The arms of the entries: what the forward saves per row, what l == 0 would ask for, and whether the family is the
+// split-bf16 one (sgf_pair_*_x3_*: SGF_F32_BF16X3 only).
 struct PaArm {
   bool softmax;
   const char *saved, *no_keys;
+  bool x3;
 };
-constexpr PaArm kSigmoidArm = {false, "rowsum", "a row sum over no keys"};
-constexpr PaArm kSoftmaxArm = {true, "lse", "a softmax over no keys"};
+constexpr PaArm kSigmoidArm = {false, "rowsum", "a row sum over no keys", false};
+constexpr PaArm kSoftmaxArm = {true, "lse", "a softmax over no keys", false};
+constexpr PaArm kSigmoidArmX3 = {false, "rowsum", "a row sum over no keys", true};
+constexpr PaArm kSoftmaxArmX3 = {true, "lse", "a softmax over no keys", true};
 
 // check_pa, then the score scale of the softmax arm
 int check_pa_arm(const char* fn, const PaArm& arm, float scale, int64_t n, int64_t l, int heads, int v_heads, int d, int dtype) {
-  if (int rc = check_pa(fn, n, l, heads, v_heads, d, dtype)) return rc;
+  if (int rc = check_pa(fn, arm.x3, n, l, heads, v_heads, d, dtype)) return rc;
   SGF_REQUIRE(!arm.softmax || (std::isfinite(scale) && scale > 0.f), SGF_E_INVALID, "%s: scale must be finite and positive (%g)",
               fn, static_cast<double>(scale));
   return SGF_OK;
 }
 
-// one launch over the storage dtype, the width and the arm; the score scale is the second kernel argument of every kernel but
-// the sigmoid forward (the sigmoid policy never reads it)
+// one launch over the storage dtype (SGF_F32_BF16X3: the f32x3 kernels), the width and the arm; the score scale is the second
+// kernel argument of every kernel but the sigmoid forward (the sigmoid policy never reads it)
 template <template <typename, int> class Launch>
 int pa_dispatch(const PaArm& arm, int d, int dtype, const PaArgs& a, float scale, dim3 grid, hipStream_t st) {
-  return by_dtype(dtype, [&](auto t) {
+  auto launch = [&](auto t) {
     using T = decltype(t);
     if (d == 32) Launch<T, 32>::run(arm.softmax, a, scale, grid, st);
     else if (d == 64) Launch<T, 64>::run(arm.softmax, a, scale, grid, st);
     else Launch<T, 128>::run(arm.softmax, a, scale, grid, st);
     SGF_LAUNCH_CHECK();
     return static_cast<int>(SGF_OK);
-  });
+  };
+  return dtype == SGF_F32_BF16X3 ? launch(f32x3{}) : by_dtype(dtype, launch);
 }
 template <typename T, int D>
 struct PaFwd {
@@ -598,8 +720,8 @@ size_t pa_workspace_bytes(int64_t n, int64_t l, int heads) {
   return static_cast<size_t>(n) * heads * sizeof(float);
 }
 
-int64_t pa_lap_rows(const char* fn, int which, int heads, int d, int dtype, int laps) {
-  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype)) {
+int64_t pa_lap_rows(const char* fn, int which, int heads, int d, int dtype, int laps, bool x3 = false) {
+  if (which < 0 || which > 2 || laps < 1 || !pa_shape_ok(heads, heads, d, dtype, x3)) {
     set_error("%s: which=%d (0 fwd, 1 bwd_q, 2 bwd_kv), laps=%d, heads=%d, d=%d, dtype %d", fn, which, laps, heads, d, dtype);
     return -1;
   }
@@ -737,5 +859,71 @@ extern "C" int sgf_pair_softmax_bwd_kv(const void* g, int64_t ldg, const float* 
                                        int64_t lddk, void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes,
                                        void* stream) {
   return pa_bwd_kv("sgf_pair_softmax_bwd_kv", kSoftmaxArm, scale, g, ldg, lse, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d,
+                   dtype, dk, lddk, dv, lddv, workspace, workspace_bytes, stream);
+}
+
+// ---- block N9: the sigmoid arm on split-bf16 products (SGF_F32_BF16X3 only) -----------------------------------------
+extern "C" int32_t sgf_pair_sigmoid_x3_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype) {
+  return pa_shape_ok(heads, v_heads, d, dtype, true) ? 1 : 0;
+}
+
+extern "C" int64_t sgf_pair_sigmoid_x3_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
+  return pa_lap_rows("sgf_pair_sigmoid_x3_lap_rows", which, heads, d, dtype, laps, true);
+}
+
+extern "C" int sgf_pair_sigmoid_x3_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                    int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* out,
+                                    int64_t ldo, float* rowsum, void* stream) {
+  return pa_fwd("sgf_pair_sigmoid_x3_fwd", kSigmoidArmX3, 1.0f, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d, dtype, out, ldo,
+                rowsum, stream);
+}
+
+extern "C" int sgf_pair_sigmoid_x3_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* rowsum,
+                                      const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                      int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dq,
+                                      int64_t lddq, void* workspace, size_t workspace_bytes, void* stream) {
+  return pa_bwd_q("sgf_pair_sigmoid_x3_bwd_q", kSigmoidArmX3, 1.0f, g, ldg, out, ldo, rowsum, q, ldq, k, ldk, v, ldv, n, l, heads,
+                  v_heads, d, dtype, dq, lddq, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgf_pair_sigmoid_x3_bwd_kv(const void* g, int64_t ldg, const float* rowsum, const void* q, int64_t ldq,
+                                       const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                                       int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, void* dk, int64_t lddk,
+                                       void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes, void* stream) {
+  return pa_bwd_kv("sgf_pair_sigmoid_x3_bwd_kv", kSigmoidArmX3, 1.0f, g, ldg, rowsum, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d,
+                   dtype, dk, lddk, dv, lddv, workspace, workspace_bytes, stream);
+}
+
+// ---- block N9: the exact softmax arm on split-bf16 products (SGF_F32_BF16X3 only) -----------------------------------
+extern "C" int32_t sgf_pair_softmax_x3_supported(int32_t heads, int32_t v_heads, int32_t d, int32_t dtype) {
+  return pa_shape_ok(heads, v_heads, d, dtype, true) ? 1 : 0;
+}
+
+extern "C" int64_t sgf_pair_softmax_x3_lap_rows(int32_t which, int32_t heads, int32_t d, int32_t dtype, int32_t laps) {
+  return pa_lap_rows("sgf_pair_softmax_x3_lap_rows", which, heads, d, dtype, laps, true);
+}
+
+extern "C" int sgf_pair_softmax_x3_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                    int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale,
+                                    void* out, int64_t ldo, float* lse, void* stream) {
+  return pa_fwd("sgf_pair_softmax_x3_fwd", kSoftmaxArmX3, scale, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d, dtype, out, ldo, lse,
+                stream);
+}
+
+extern "C" int sgf_pair_softmax_x3_bwd_q(const void* g, int64_t ldg, const void* out, int64_t ldo, const float* lse,
+                                      const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                      int64_t n, int64_t l, int32_t heads, int32_t v_heads, int32_t d, int32_t dtype,
+                                      float scale, void* dq, int64_t lddq, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return pa_bwd_q("sgf_pair_softmax_x3_bwd_q", kSoftmaxArmX3, scale, g, ldg, out, ldo, lse, q, ldq, k, ldk, v, ldv, n, l, heads,
+                  v_heads, d, dtype, dq, lddq, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgf_pair_softmax_x3_bwd_kv(const void* g, int64_t ldg, const float* lse, const void* q, int64_t ldq,
+                                       const void* k, int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l,
+                                       int32_t heads, int32_t v_heads, int32_t d, int32_t dtype, float scale, void* dk,
+                                       int64_t lddk, void* dv, int64_t lddv, const void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  return pa_bwd_kv("sgf_pair_softmax_x3_bwd_kv", kSoftmaxArmX3, scale, g, ldg, lse, q, ldq, k, ldk, v, ldv, n, l, heads, v_heads, d,
                    dtype, dk, lddk, dv, lddv, workspace, workspace_bytes, stream);
 }

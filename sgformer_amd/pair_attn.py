@@ -13,6 +13,11 @@ not take stays on difformer._dense_attention.  `use_kernels(q, k, v)` adds the s
 path, 1 = the kernels wherever supported, unset = the kernels from PAIR_MIN_PAIRS (fp32) / PAIR_MIN_PAIRS_BF16 score
 entries (n l H) upward.
 
+fp32 tensors under torch.set_float32_matmul_precision('high') run the split-bf16 kernels (the sgf_pair_*_x3_* entries of
+block N9, dtype code SGF_F32_BF16X3: every matrix product as three bf16 matrix-core products, everything else in fp32)
+wherever sgf_pair_*_x3_supported takes the shape, chosen at each launch as kernels._mm_code chooses for every other
+product; 'highest' and bf16 tensors run what they always ran.  Their thresholds are PAIR_MIN_PAIRS_X3 / SOFTMAX_MIN_PAIRS_X3.
+
 The exact softmax attention of medium/ablation/oursSOFT.py runs on the same skeleton with an online maximum (include/sgf.h
 block N8):
 
@@ -29,12 +34,13 @@ import os
 
 import torch
 
-from . import _lib, ops
-from .kernels import _code, _launch
+from . import _lib, kernels, ops
+from .kernels import _launch
 from .linear import _switch
 
-__all__ = ["sigmoid_attention", "supported", "use_kernels", "PAIR_MIN_PAIRS",
-           "softmax_attention", "softmax_supported", "use_softmax_kernels", "SOFTMAX_MIN_PAIRS", "SOFTMAX_MIN_PAIRS_BF16"]
+__all__ = ["sigmoid_attention", "supported", "use_kernels", "PAIR_MIN_PAIRS", "PAIR_MIN_PAIRS_X3",
+           "softmax_attention", "softmax_supported", "use_softmax_kernels", "SOFTMAX_MIN_PAIRS", "SOFTMAX_MIN_PAIRS_BF16",
+           "SOFTMAX_MIN_PAIRS_X3"]
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16
@@ -44,19 +50,25 @@ _BF16 = torch.bfloat16
 # probed head count (profiles/pair_attn_probe.md says how it follows from the table).  0: ahead at every probed size.
 PAIR_MIN_PAIRS = 19717 * 19717 * 4      # fp32 storage: the exact fp32 matrix cores against a library GEMM that keeps its scores
 PAIR_MIN_PAIRS_BF16 = 0                 # bf16 storage
+# fp32 storage when the split-bf16 kernels would run ('high'), against the dense path under the same setting, whose library GEMMs
+# gain from it too (profiles/pair_x3_probe.md): the kernels are 1.3 - 1.8 x the exact ones, and the last probed cell that is not
+# ahead beyond the spread is 40 000 nodes x 1 head at D = 128 (forward + backward level with the dense path).
+PAIR_MIN_PAIRS_X3 = 40000 * 40000 * 2
 
 # The same rule for the softmax kernels under SGF_PAIR_SOFTMAX (profiles/pair_softmax_probe.md; widths 32 / 64 / 128 and 1 / 2 / 4
 # heads were probed).  With one head the dense path is two plain GEMMs around a softmax and stays ahead in time up to the largest
 # probed size (while holding gigabytes of scores): the smallest size from which every probed cell is ahead is 40 000 nodes x 2 heads.
 SOFTMAX_MIN_PAIRS = 40000 * 40000 * 2        # fp32 storage
 SOFTMAX_MIN_PAIRS_BF16 = 40000 * 40000 * 2   # bf16 storage
+SOFTMAX_MIN_PAIRS_X3 = 40000 * 40000 * 2     # fp32 storage on the split-bf16 kernels under 'high' (profiles/pair_x3_probe.md)
 
 
 # The two arms.  An arm is told by its entry family ("pair_sigmoid" / "pair_softmax": the prefix of the sgf_* entries and of the
-# kernel table's methods); here is what else differs: the public function's name, its switch and its two thresholds (module
-# attributes, looked up by name on every call).
-_ARMS = {"pair_sigmoid": ("sigmoid_attention", "SGF_PAIR_ATTN", "PAIR_MIN_PAIRS", "PAIR_MIN_PAIRS_BF16"),
-         "pair_softmax": ("softmax_attention", "SGF_PAIR_SOFTMAX", "SOFTMAX_MIN_PAIRS", "SOFTMAX_MIN_PAIRS_BF16")}
+# kernel table's methods); here is what else differs: the public function's name, its switch and its three thresholds (module
+# attributes, looked up by name on every call: fp32, bf16, fp32 on the split-bf16 kernels).
+_ARMS = {"pair_sigmoid": ("sigmoid_attention", "SGF_PAIR_ATTN", "PAIR_MIN_PAIRS", "PAIR_MIN_PAIRS_BF16", "PAIR_MIN_PAIRS_X3"),
+         "pair_softmax": ("softmax_attention", "SGF_PAIR_SOFTMAX", "SOFTMAX_MIN_PAIRS", "SOFTMAX_MIN_PAIRS_BF16",
+                          "SOFTMAX_MIN_PAIRS_X3")}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -69,13 +81,27 @@ def _hip_supported(family: str, heads: int, v_heads: int, d: int, dtype) -> bool
                                                                 _lib.SGF_BF16 if dtype == _BF16 else _lib.SGF_F32))
 
 
+def _entry(family: str, launch: str, q, hv: int):
+    """(entry name, dtype code) of one launch, decided when it is made: fp32 operands under 'high' go to the split-bf16
+    family with SGF_F32_BF16X3 where sgf_<family>_x3_supported takes the shape; everything else is the exact family with the
+    storage code."""
+    code = kernels._mm_code(q, f"sgf_{family}_x3_supported", q.shape[1], hv, q.shape[2])
+    if code == _lib.SGF_F32_BF16X3:
+        return f"sgf_{family}_x3_{launch}", code
+    return f"sgf_{family}_{launch}", code
+
+
+def _x3_would_run(family: str, q, v) -> bool:
+    return q.dtype == _F32 and _entry(family, "fwd", q, v.shape[1])[1] == _lib.SGF_F32_BF16X3
+
+
 # `scale`: () for the sigmoid entries, (scale,) for the softmax entries, whose argument lists have it after the dtype code
 def _hip_fwd(family: str, scale: tuple, q, k, v):
     dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
     out = torch.empty((n, h, d), dtype=q.dtype, device=dev)
     saved = torch.empty((n, h), dtype=_F32, device=dev)
-    _launch(dev, f"sgf_{family}_fwd", q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, _code(q), *scale, out,
-            h * d, saved)
+    entry, code = _entry(family, "fwd", q, hv)
+    _launch(dev, entry, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, code, *scale, out, h * d, saved)
     return out, saved
 
 
@@ -83,8 +109,9 @@ def _hip_bwd_q(family: str, scale: tuple, g, out, saved, q, k, v, want_dq: bool)
     dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
     dq = torch.empty((n, h, d), dtype=q.dtype, device=dev) if want_dq else None
     delta = torch.empty((n, h), dtype=_F32, device=dev)
-    _launch(dev, f"sgf_{family}_bwd_q", g, g.stride(0), out, out.stride(0), saved, q, q.stride(0), k, k.stride(0), v,
-            v.stride(0), n, l, h, hv, d, _code(q), *scale, dq, h * d, delta, delta.numel() * 4)
+    entry, code = _entry(family, "bwd_q", q, hv)
+    _launch(dev, entry, g, g.stride(0), out, out.stride(0), saved, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h,
+            hv, d, code, *scale, dq, h * d, delta, delta.numel() * 4)
     return dq, delta
 
 
@@ -92,8 +119,9 @@ def _hip_bwd_kv(family: str, scale: tuple, g, saved, delta, q, k, v):
     dev, (n, h, d), l, hv = q.device, q.shape, k.shape[0], v.shape[1]
     dk = torch.empty((l, h, d), dtype=q.dtype, device=dev)
     dv = torch.empty((l, hv, d), dtype=q.dtype, device=dev)
-    _launch(dev, f"sgf_{family}_bwd_kv", g, g.stride(0), saved, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d,
-            _code(q), *scale, dk, h * d, dv, hv * d, delta, delta.numel() * 4)
+    entry, code = _entry(family, "bwd_kv", q, hv)
+    _launch(dev, entry, g, g.stride(0), saved, q, q.stride(0), k, k.stride(0), v, v.stride(0), n, l, h, hv, d, code, *scale,
+            dk, h * d, dv, hv * d, delta, delta.numel() * 4)
     return dk, dv
 
 
@@ -167,14 +195,21 @@ def _supported(q, k, v, family: str) -> bool:
 
 def _use(q, k, v, family: str) -> bool:
     """_supported under the arm's switch (read on every call): 0 = always the dense path, 1 = the kernels wherever supported,
-    unset = the kernels from the arm's threshold for the storage dtype (n l H score entries) upward."""
-    _, switch, min_pairs, min_pairs_bf16 = _ARMS[family]
+    unset = the kernels from the arm's threshold (n l H score entries) upward: the one for bf16 storage, for fp32 storage, or
+    for fp32 storage when the HIP table would run the split-bf16 kernels."""
+    _, switch, min_pairs, min_pairs_bf16, min_pairs_x3 = _ARMS[family]
     s = os.environ.get(switch)
     if s is not None and not _switch(switch, True):
         return False
     if not _supported(q, k, v, family):
         return False
-    return s is not None or q.shape[0] * k.shape[0] * q.shape[1] >= globals()[min_pairs_bf16 if q.dtype == _BF16 else min_pairs]
+    if s is not None:
+        return True
+    if q.dtype == _BF16:
+        name = min_pairs_bf16
+    else:
+        name = min_pairs_x3 if _table(family + "_fwd") is _Hip and _x3_would_run(family, q, v) else min_pairs
+    return q.shape[0] * k.shape[0] * q.shape[1] >= globals()[name]
 
 
 def supported(q, k, v) -> bool:
