@@ -523,16 +523,7 @@ def test_sum_n_and_fan_out(cuda, dtype, k):
 # ------------------------------------------------------------------------------------------------
 # N1 induced subgraph (sgf_subgraph_*): bit-exact against the PyG 1.7.2 semantics
 # ------------------------------------------------------------------------------------------------
-def _ref_subgraph(subset, ei, n, relabel):
-    mask_n = torch.zeros(n, dtype=torch.bool)
-    mask_n[subset] = True
-    keep = mask_n[ei[0]] & mask_n[ei[1]]
-    out = ei[:, keep]
-    if relabel:
-        idx = torch.zeros(n, dtype=torch.int64)
-        idx[subset] = torch.arange(subset.numel())
-        out = idx[out]
-    return out, keep
+from tests.graph_ladder import ref_subgraph as _ref_subgraph   # noqa: E402  (the mask-and-relabel restatement, shared)
 
 
 @pytest.mark.parametrize("n,nnz,m", [(1000, 20000, 300), (50000, 1500000, 7000), (257, 513, 257), (100, 4000, 0),
