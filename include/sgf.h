@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 669 /* 0.6.15: sgf_pair_sigmoid_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv and sgf_pair_softmax_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv, the all-pair attention kernels for SGF_F32_BF16X3 (csrc/pair_attn.hip); 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 670 /* 0.6.16: sgf_gat_supported / _lap_rows / sgf_gat_scores / _fwd / _bwd_dst / _bwd_src, attention over the stored entries of a CSR (GATConv's edge softmax, block N10, csrc/gat.hip); 0.6.15: sgf_pair_sigmoid_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv and sgf_pair_softmax_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv, the all-pair attention kernels for SGF_F32_BF16X3 (csrc/pair_attn.hip); 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -1257,6 +1257,62 @@ int sgf_pair_softmax_x3_bwd_kv(const void* g, int64_t ldg, const float* lse, con
                                int64_t ldk, const void* v, int64_t ldv, int64_t n, int64_t l, int32_t heads, int32_t v_heads,
                                int32_t d, int32_t dtype, float scale, void* dk, int64_t lddk, void* dv, int64_t lddv,
                                const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * N10 — attention over the stored entries of a CSR: torch_geometric 1.7.2 GATConv without an [E, H] or [E, H, C] tensor,
+ * forward or backward (csrc/gat.hip).  H heads of C channels; xw [n_src, H * C] is the projected input, row-major with
+ * leading dimension ldx.  Per head h, for entry e of target row i with source j = colind[e] (val is not read; parallel
+ * entries each count):
+ *     al[n, h] = <xw[n, h, :], att_l[h, :]>      ar likewise with att_r                                 (sgf_gat_scores)
+ *     z_e = al[j, h] + ar[i, h]      s_e = z_e > 0 ? z_e : negative_slope z_e
+ *     m = max_e s_e   l = sum_e exp(s_e - m)   p_e = exp(s_e - m) / l   lse = m + log l   norm = (m, 1 / l)
+ *     p~_e = p_e keep_e / (1 - p_drop)      out[i, h, :] = sum_e p~_e xw[j, h, :]                          (sgf_gat_fwd)
+ *   out is [n_rows, H * C], or with mean_heads != 0 the mean over the heads [n_rows, C]; `bias` (fp32, H * C or C values,
+ *   may be NULL) is added last.  An empty row gives bias alone, lse = 0, norm = (0, 0), and nothing in the backward.  The
+ *   entries of a row are walked once with an online maximum (a rise rescales l and the accumulators by exp(m - m')).
+ *   With g_h = g[i, h, :] (mean_heads: g[i, :] / H for every head) and dp_e = <g_h, xw[j, h, :]>:
+ *     delta[i, h] = sum_e p~_e dp_e
+ *     dz_e = p_e (keep_e / (1 - p_drop) dp_e - delta[i, h]) sl_e            sl_e = z_e > 0 ? 1 : negative_slope
+ *     dar[i, h] = sum_{e in row i} dz_e = B - delta S,  B = sum p~ dp sl,  S = sum p sl                (sgf_gat_bwd_dst)
+ *     dal[j, h] = sum_{e: colind[e] = j} dz_e
+ *     dxw[j, h, :] = sum_{e: colind[e] = j} p~_e g_h[i] + dal[j, h] att_l[h, :] + dar[j, h] att_r[h, :]  (sgf_gat_bwd_src)
+ *   sgf_gat_bwd_src walks the TRANSPOSED CSR (row = source j, entries = its targets i; sgf_csr_transpose) and runs after
+ *   sgf_gat_bwd_dst, whose delta and dar it reads; att_l / att_r may be NULL (no score term of that side; dar may then be
+ *   NULL too), and the dar term is added for j < n_rows only (targets are the first n_rows sources).  Both backward
+ *   launches recompute p_e = exp(s_e - m) / l from al, ar and norm: through the fp32 lse the weights of a row of 2^k equal
+ *   scores would not come out as 2^-k.  al, ar, lse [., H], norm [n_rows, H, 2], delta, dar, dal are fp32; xw, g, out, dxw
+ *   are fp32 or bf16 (dtype), accumulated in fp32 and rounded once.
+ * Keep decisions (p_drop > 0): Philox4x32-10 with the round function and key schedule of sgf_dropout, key = seed, counter
+ *   (i, j, 0x53474154, h / 4); head h reads word h % 4 and is kept when (word >> 8) 2^-24 >= p_drop.  The decision is a
+ *   function of (target, source, head): the same in both orientations, and shared by parallel entries i <- j.
+ * No atomics; every sum runs in stored order inside one group of lanes: bit-reproducible.  A row of any length is walked by
+ *   its one group of lanes.
+ * Shapes (sgf_gat_supported): 1 <= heads <= 8, c % 4 == 0, heads * c <= 1024, SGF_F32 or SGF_BF16; else SGF_E_UNSUPPORTED.
+ * Checks, in this order, all before the first HIP call: negative sizes (SGF_E_INVALID); shape and dtype; more than 2^31 - 1
+ *   rows (SGF_E_UNSUPPORTED); negative_slope finite and 0 <= p_drop <= 1 (SGF_E_INVALID); nothing to walk (n, n_rows or, for
+ *   bwd_src, n_src == 0): SGF_OK; null pointers; a leading dimension below the width (H * C, or C for out / g under
+ *   mean_heads); rows not aligned to what a lane moves (4 channels: pointers % 16 bytes for fp32, % 8 for bf16, leading
+ *   dimensions % 4 elements); att_l / att_r / bias not 16-byte aligned.
+ * sgf_gat_lap_rows: rows one lap of the capped grid of kernel `which` (0 scores, 1 fwd, 2 bwd_dst, 3 bwd_src) covers (a
+ *   launch over more rows gives a workgroup several laps), -1 for a bad argument.  Host query, no GPU needed.
+ * ------------------------------------------------------------------------------------------ */
+int32_t sgf_gat_supported(int32_t heads, int32_t c, int32_t dtype);
+int64_t sgf_gat_lap_rows(int32_t heads, int32_t c, int32_t dtype, int32_t which);
+int sgf_gat_scores(const void* xw, int64_t ldx, const float* att_l, const float* att_r, int64_t n, int32_t heads, int32_t c,
+                   int32_t dtype, float* al, float* ar, void* stream);
+int sgf_gat_fwd(const int64_t* rowptr, const int32_t* colind, const void* xw, int64_t ldx, const float* al, const float* ar,
+                const float* bias, int64_t n_rows, int64_t n_src, int32_t heads, int32_t c, int32_t dtype, int32_t mean_heads,
+                float negative_slope, float p_drop, uint64_t seed, void* out, int64_t ldo, float* lse, float* norm,
+                void* stream);
+int sgf_gat_bwd_dst(const int64_t* rowptr, const int32_t* colind, const void* g, int64_t ldg, const void* xw, int64_t ldx,
+                    const float* al, const float* ar, const float* norm, int64_t n_rows, int64_t n_src, int32_t heads,
+                    int32_t c, int32_t dtype, int32_t mean_heads, float negative_slope, float p_drop, uint64_t seed,
+                    float* delta, float* dar, void* stream);
+int sgf_gat_bwd_src(const int64_t* t_rowptr, const int32_t* t_colind, const void* g, int64_t ldg, const void* xw, int64_t ldx,
+                    const float* al, const float* ar, const float* norm, const float* delta, const float* dar,
+                    const float* att_l, const float* att_r, int64_t n_rows, int64_t n_src, int32_t heads, int32_t c,
+                    int32_t dtype, int32_t mean_heads, float negative_slope, float p_drop, uint64_t seed, float* dal, void* dxw,
+                    int64_t lddx, void* stream);
 
 /* y = sum_i xs[i] for 1 <= k <= 8 equally shaped [n, d] operands (fp32 accumulation in operand
  * order).  Replaces the pairwise gradient accumulation autograd performs for a tensor with several

@@ -3,6 +3,7 @@
     sgformer_amd.ours          drop-in for large/ours.py (SGFormer, TransConv, GraphConv, ...)
     sgformer_amd.ours_100m     drop-in for 100M/ours.py (alpha residual, neighbour-sampled batches)
     sgformer_amd.ours_medium   drop-in for medium/ours.py + the models.GCN backbone (GCNConv on libsgf)
+    sgformer_amd.gat           the GAT backbone of the medium recipes (GATConv / GAT on the edge-softmax kernels)
     sgformer_amd.difformer     drop-in for medium/difformer.py (DIFFormer, simple kernel)
     sgformer_amd.ours_soft     drop-in for medium/ablation/oursSOFT.py (SGFormerSOFT, exact softmax attention)
     sgformer_amd.ops           autograd operators over the C ABI (include/sgf.h -> lib/libsgf.so)

@@ -234,6 +234,15 @@ SIGNATURES = {
                                             _P]),
     "sgf_pair_softmax_x3_bwd_kv": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int32,
                                              c_int32, c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, c_size_t, _P]),
+    "sgf_gat_supported": (c_int32, [c_int32, c_int32, c_int32]),
+    "sgf_gat_lap_rows": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "sgf_gat_scores": (c_int32, [_P, c_int64, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "sgf_gat_fwd": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_float,
+                              c_float, c_uint64, _P, c_int64, _P, _P, _P]),
+    "sgf_gat_bwd_dst": (c_int32, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                  c_int32, c_float, c_float, c_uint64, _P, _P, _P]),
+    "sgf_gat_bwd_src": (c_int32, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32,
+                                  c_int32, c_int32, c_int32, c_float, c_float, c_uint64, _P, _P, c_int64, _P]),
     "sgf_sum_n": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_int32, _P, c_int64, _P]),
     "sgf_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "sgf_colsum": (c_int32, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, c_size_t, _P]),

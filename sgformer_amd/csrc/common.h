@@ -146,6 +146,16 @@ __device__ __forceinline__ void store1<float>(float* p, float f) { *p = f; }
 template <>
 __device__ __forceinline__ void store1<uint16_t>(uint16_t* p, float f) { *p = f32_to_bf16(f); }
 
+// ---- Philox4x32-10 (Salmon et al., SC11): the round function, shared by the dropout of csrc/fused.hip and csrc/gat.hip ----
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c[0];
+  const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * c[2];
+  const uint32_t hi0 = static_cast<uint32_t>(p0 >> 32), lo0 = static_cast<uint32_t>(p0);
+  const uint32_t hi1 = static_cast<uint32_t>(p1 >> 32), lo1 = static_cast<uint32_t>(p1);
+  const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
 // ---- T1: value of one stored entry of the normalised adjacency (large/ours.py:28-31), shared by csr.hip / subgraph_csr.hip ----
 __device__ __forceinline__ float norm_value(int32_t deg_tgt, int32_t deg_src) {
 #pragma clang fp contract(off)

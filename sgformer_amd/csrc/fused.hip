@@ -1078,15 +1078,7 @@ __global__ __launch_bounds__(kThreads) void k_sum_n_bf16x8(SumArgs a, int64_t n,
 // (seed, element index) — Philox4x32-10, one counter per 4 consecutive elements of a row — so the
 // backward recomputes them.  ATen's native_dropout writes and re-reads an [N, d] mask.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c[0];
-  const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * c[2];
-  const uint32_t hi0 = static_cast<uint32_t>(p0 >> 32), lo0 = static_cast<uint32_t>(p0);
-  const uint32_t hi1 = static_cast<uint32_t>(p1 >> 32), lo1 = static_cast<uint32_t>(p1);
-  const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
+// (philox_round: csrc/common.h)
 // 4 keep flags (bit j = element 4*chunk + j is kept) for chunk index `chunk` under `seed`
 __device__ __forceinline__ uint32_t dropout_keep4(uint64_t seed, uint64_t chunk, float p) {
   uint32_t c[4] = {static_cast<uint32_t>(chunk), static_cast<uint32_t>(chunk >> 32), 0x5347464du, 0u};

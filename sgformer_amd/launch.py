@@ -86,6 +86,16 @@ def patch_medium_gcn():
     return models
 
 
+def patch_medium_gat():
+    """medium/parse.py builds the `--backbone gat` branch (and `--method gat`) from the reference's `models.GAT` (PyG GATConv).
+    As patch_medium_gcn: point the trainer's `models.GAT` at the libsgf one (sgformer_amd.gat.GAT) — same class name,
+    constructor and state_dict keys."""
+    import importlib as _il
+    models = _il.import_module("models")
+    models.GAT = _il.import_module("sgformer_amd.gat").GAT
+    return models
+
+
 def patch_100m_data_utils():
     """100M/nb-sample.py:12 imports `load_fixed_splits` from 100M/data_utils.py, which does not define it — the trainer
     cannot be imported as shipped.  Import the trainer's own data_utils (its directory is on sys.path by now) and add the
@@ -511,6 +521,7 @@ def main(argv=None):
     sys.path.insert(0, tdir)
     if variant == "medium":
         patch_medium_gcn()
+        patch_medium_gat()
     if variant in ("100M", "100m"):
         patch_100m_data_utils()
     _select_device(argv)
