@@ -8,7 +8,7 @@ ifdef PROBES
 HIPFLAGS += -DSGF_PROBES
 endif
 CSRC := sgformer_amd/csrc
-SRCS := $(CSRC)/capi.hip $(CSRC)/csr.hip $(CSRC)/spmm.hip $(CSRC)/attn.hip $(CSRC)/fused.hip $(CSRC)/subgraph.hip $(CSRC)/reorder.hip $(CSRC)/spmm_plan.hip $(CSRC)/prologue.hip $(CSRC)/head.hip $(CSRC)/rowgemm.hip $(CSRC)/spmm_tile.hip $(CSRC)/spmm_pack.hip $(CSRC)/sampler.hip $(CSRC)/linear_f32.hip $(CSRC)/gemm.hip $(CSRC)/attn_small.hip $(CSRC)/comm.hip $(CSRC)/subgraph_csr.hip $(CSRC)/gramx.hip $(CSRC)/linear_f32x.hip $(CSRC)/gram_f32x.hip $(CSRC)/attn_f32x.hip $(CSRC)/bce.hip $(CSRC)/metrics.hip $(CSRC)/sampled_csr.hip $(CSRC)/head_rows.hip $(CSRC)/pair_attn.hip $(CSRC)/gat.hip
+SRCS := $(CSRC)/capi.hip $(CSRC)/csr.hip $(CSRC)/spmm.hip $(CSRC)/attn.hip $(CSRC)/fused.hip $(CSRC)/subgraph.hip $(CSRC)/reorder.hip $(CSRC)/spmm_plan.hip $(CSRC)/prologue.hip $(CSRC)/head.hip $(CSRC)/rowgemm.hip $(CSRC)/spmm_tile.hip $(CSRC)/spmm_pack.hip $(CSRC)/sampler.hip $(CSRC)/linear_f32.hip $(CSRC)/gemm.hip $(CSRC)/attn_small.hip $(CSRC)/comm.hip $(CSRC)/subgraph_csr.hip $(CSRC)/gramx.hip $(CSRC)/linear_f32x.hip $(CSRC)/gram_f32x.hip $(CSRC)/attn_f32x.hip $(CSRC)/bce.hip $(CSRC)/metrics.hip $(CSRC)/sampled_csr.hip $(CSRC)/head_rows.hip $(CSRC)/pair_attn.hip $(CSRC)/gat.hip $(CSRC)/spmm_coded.hip
 BUILD ?= build
 OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(SRCS))
 LIB  ?= sgformer_amd/lib/libsgf.so

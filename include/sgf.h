@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SGF_VERSION 670 /* 0.6.16: sgf_gat_supported / _lap_rows / sgf_gat_scores / _fwd / _bwd_dst / _bwd_src, attention over the stored entries of a CSR (GATConv's edge softmax, block N10, csrc/gat.hip); 0.6.15: sgf_pair_sigmoid_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv and sgf_pair_softmax_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv, the all-pair attention kernels for SGF_F32_BF16X3 (csrc/pair_attn.hip); 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
+#define SGF_VERSION 671 /* 0.6.17: sgf_spmm_coded_bytes / sgf_spmm_coded_supported / sgf_spmm_code_rows / sgf_spmm_code_values / sgf_spmm_coded, the SpMM gathering lossless 12-bit coded operand rows with the row scale folded into the CSR values (csrc/spmm_coded.hip, csrc/spmm.hip); 0.6.16: sgf_gat_supported / _lap_rows / sgf_gat_scores / _fwd / _bwd_dst / _bwd_src, attention over the stored entries of a CSR (GATConv's edge softmax, block N10, csrc/gat.hip); 0.6.15: sgf_pair_sigmoid_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv and sgf_pair_softmax_x3_supported / _lap_rows / _fwd / _bwd_q / _bwd_kv, the all-pair attention kernels for SGF_F32_BF16X3 (csrc/pair_attn.hip); 0.6.14: sgf_ew_lap_rows, host query for the rows one loop iteration of the capped grid covers in the persistent element-wise, LayerNorm / BatchNorm and loss kernels (csrc/fused.hip); 0.6.13: sgf_pair_softmax_supported / _workspace_bytes / _lap_rows / sgf_pair_softmax_fwd / _bwd_q / _bwd_kv, the exact softmax all-pair attention as tiled products with an online maximum (csrc/pair_attn.hip); 0.6.12: sgf_pair_sigmoid_supported / _workspace_bytes / _lap_rows / sgf_pair_sigmoid_fwd / _bwd_q / _bwd_kv, DIFFormer's all-pair sigmoid attention as tiled products without the n x l score tensor (csrc/pair_attn.hip); 0.6.11: sgf_head_rows_supported / _fwd_workspace_bytes / _bwd_workspace_bytes / sgf_head_rows_fwd / sgf_head_rows_bwd, the head, its cross-entropy and their gradient on the selected (seed) rows of a sampled batch (csrc/head_rows.hip); 0.6.10: sgf_row_lap_rows, host query for the rows one lap of the persistent bf16 row kernels covers (csrc/rowgemm.hip, csrc/head.hip); 0.6.9: sgf_bn_apply_packed / sgf_spmm_packed / sgf_spmm_packed_supported / sgf_spmm_packed_bytes, the forward GCN SpMM gathering zero-elided operand rows (csrc/fused.hip, csrc/spmm.hip); 0.6.8: sgf_spmm_arm / sgf_spmm_blocked_arm, host queries for the kernel a SpMM launch would run; 0.6.7: sgf_attn_max_blocks / sgf_attn_tile_rows, host queries for the grid cap and tile heights of the persistent attention kernels; 0.6.6: sgf_dropout_dev, sgf_dropout with its 64-bit seed read from device memory when the kernel runs (a launch captured into a hipGraph draws a new mask per replay); 0.6.5: sgf_sampled_csr_supported / _build_workspace_bytes / _build / _transpose_workspace_bytes / _transpose, the normalised CSR of a neighbour-sampled batch and its transpose without the edge-list sort (csrc/sampled_csr.hip); 0.6.4: sgf_rocauc_workspace_bytes / sgf_rocauc_counts / sgf_argmax_workspace_bytes / sgf_argmax_count, the evaluation metrics as integer counts (csrc/metrics.hip); 0.6.3: sgf_attn_h_supported; sgf_attn_h_fwd / _bwd_reduce / _bwd_apply take SGF_F32_BF16X3 (csrc/attn_f32x.hip); 0.6.2: sgf_bce_workspace_bytes / sgf_bce_fwd / sgf_bce_bwd, the multi-label loss on the training rows (csrc/bce.hip); 0.6.1: dtype code SGF_F32_BF16X3 (csrc/linear_f32x.hip, csrc/gram_f32x.hip) */
 
 #define SGF_F32 0
 #define SGF_BF16 1
@@ -210,6 +210,41 @@ int sgf_spmm_packed(const int64_t* rowptr, const int32_t* colind, const float* v
                     int64_t n_cols, const void* packed, int32_t slot_bytes, const int32_t* overflow, void* y, int64_t ldy,
                     int64_t n_rows, int32_t d, int32_t dtype, int64_t long_len, int64_t long_segments, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* sgf_spmm_split with a lossless 12-BIT CODED copy of x next to the dense one (bf16, d = 256).  A bf16 value is
+ * s | Ek (8) | m (7).  Per row of x, E = the largest exponent field Ek among its finite non-zero elements (15 if it has
+ * none); an element is coded s | e | m with e = Ek - (E - 15) in 1..15, a zero of either sign s | 0 | 0: 256 x 12 bits =
+ * 384 bytes, 3 fetch lines where the dense row takes 4.  Placing e in the low four bits of an fp32 exponent field decodes
+ * a zero to itself and any other element to a normal float d of [2^-126, 2^-111) with element = d * 2^(E - 15), exactly.
+ * A row ESCAPES (is not coded) when an element is subnormal, Inf or NaN or lies more than 14 binades under the largest.
+ *   sgf_spmm_code_rows    one pass over x: `coded` (sgf_spmm_coded_bytes(n) bytes, 128-byte aligned) takes the slots,
+ *                         scale_u8[r] = E of row r or 255 for an escaped row (its slot is zero bytes), *n_escaped (device
+ *                         int32) the number of escaped rows (scale_u8 16-byte aligned).  Slot: dword l (l = 0..63, byte 4 l) holds columns 4l, 4l+1
+ *                         and the exponents of 4l+2, 4l+3 — bits 15..0 s0 | e2 | e0 | m0, bits 31..16 s1 | e3 | e1 | m1 —
+ *                         and half l (byte 256 + 2 l) bits 7..0 s2 | m2, bits 15..8 s3 | m3.
+ *   sgf_spmm_code_values  one pass over the CSR: val_coded[e] = val[e] * 2^(scale_u8[colind[e]] - 15) where val[e] is a
+ *                         normal float > 0, the source row is coded and the product is a normal float; else -val[e], the
+ *                         ESCAPE TAG (val 0 becomes -0.0).  *n_unsupported (device int32) counts the val[e] with the sign bit set (-0.0 included), which
+ *                         the tag cannot mark.  colind, val, val_coded 16-byte aligned.
+ *   sgf_spmm_coded        y = A x: an entry with val_coded >= 0 decodes its row from the slot and multiplies by
+ *                         val_coded — fmaf(v * 2^s, x * 2^-s, acc) is fmaf(v, x, acc) bit for bit while both factors are
+ *                         normal floats — a tagged entry reads the dense row of x and multiplies by |val_coded| = val.
+ *                         Same FMAs in the same order as sgf_spmm_split: y is equal bit for bit.  *n_unsupported != 0
+ *                         (read ON THE DEVICE) runs the whole launch on x and val.  The slots are gathered only where
+ *                         sgf_spmm_coded_supported answers 1 — the launch would run the wave-per-row kernel
+ *                         (sgf_spmm_arm = 2) on bf16 rows of exactly 256 columns, slots within 32-bit offsets,
+ *                         SGF_SPMM_CODED != 0 (cached switch) — every other launch is sgf_spmm_split's on x and val;
+ *                         rows longer than long_len are reduced from x and val as in sgf_spmm_split. */
+size_t sgf_spmm_coded_bytes(int64_t n);
+int32_t sgf_spmm_coded_supported(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols, int32_t aligned16);
+int sgf_spmm_code_rows(const void* x, int64_t ldx, int64_t n, void* coded, uint8_t* scale_u8, int32_t* n_escaped,
+                       void* stream);
+int sgf_spmm_code_values(const int32_t* colind, const float* val, int64_t nnz, const uint8_t* scale_u8, float* val_coded,
+                         int32_t* n_unsupported, void* stream);
+int sgf_spmm_coded(const int64_t* rowptr, const int32_t* colind, const float* val, const float* val_coded, const void* x,
+                   int64_t ldx, int64_t n_cols, const void* coded, const int32_t* n_unsupported, void* y, int64_t ldy,
+                   int64_t n_rows, int32_t d, int32_t dtype, int64_t long_len, int64_t long_segments, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* sgf_spmm_split for a CSR whose gathers mostly hit in L2 (a locality-restoring node order, sgf_reorder
  * below).  The vector memory pipe's address rate is per LANE, so bf16 rows (512 B) are then fetched TWO per

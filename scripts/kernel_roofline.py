@@ -116,6 +116,14 @@ def main(path: str, elem: int):
         ("k_spmm_row_packed<384>", ("k_spmm_row_packed<384",), csr + 1.75 * T,
          "layer 1 forward, gather-bound: {:.1f} GB of 384-B slot fetches per launch".format(
              (NNZ * (8 + 384) + (N + 1) * 8) / 1e9 + T), find),
+        # the SpMM on 12-bit coded rows (graph.CODED_CLASSES: layer 2's forward launch as merged):
+        # per launch one pass over the operand (T in, 0.75 T of slots + N scale bytes out), one over the CSR (8 B in, 4 B out
+        # per entry) and the gather of 384-byte slots (escaped rows: 512-byte dense rows)
+        ("k_code_rows", ("k_code_rows",), 1.75 * T + N / 1e9, "x -> 384-byte slots + scale bytes", find),
+        ("k_code_values", ("k_code_values",), NNZ * 12 / 1e9, "colind, val -> val' (scale bytes out of L2)", find),
+        ("k_spmm_row_coded", ("k_spmm_row_coded<",), csr + 1.75 * T,
+         "gather-bound: {:.1f} GB of 384-B slot fetches per launch when no row escapes".format(
+             (NNZ * (8 + 384) + (N + 1) * 8) / 1e9 + T), find),
         ("k_bn_bwd_stats_bf16x8<one gradient>", ("k_bn_bwd_stats_bf16x8<false",), 2 * T, "the three layers (g, z)", find),
         ("k_bn_bwd_stats_bf16x8<two gradients>", ("k_bn_bwd_stats_bf16x8<true",), 3 * T, "the stem (g1, g2, z)", find),
         ("k_bn_bwd_apply_bf16x8", ("k_bn_bwd_apply_bf16x8<",), 3 * T, "g, z -> dz", find),

@@ -57,6 +57,12 @@ SIGNATURES = {
     "sgf_spmm_packed_supported": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sgf_spmm_packed": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int32, _P, _P, c_int64, c_int64, c_int32, c_int32,
                                   c_int64, c_int64, _P, c_size_t, _P]),
+    "sgf_spmm_coded_bytes": (c_size_t, [c_int64]),
+    "sgf_spmm_coded_supported": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, c_int32]),
+    "sgf_spmm_code_rows": (c_int32, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "sgf_spmm_code_values": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P]),
+    "sgf_spmm_coded": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, c_int32, c_int32,
+                                 c_int64, c_int64, _P, c_size_t, _P]),
     "sgf_spmm_stream": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_int64,
                                   c_int64, _P, c_size_t, _P]),
     "sgf_reorder_workspace_bytes": (c_size_t, [c_int64, c_int64]),

@@ -238,7 +238,7 @@ struct DenseRowLoader {
   int voff;
   uint32_t pitch;
   template <int N> struct Batch { u32x2 raw[N]; };
-  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N]) const {
+  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N], const float (&)[N]) const {
 #pragma unroll
     for (int u = 0; u < N; ++u) b.raw[u] = BufRow<uint16_t>::load(rsrc, voff, static_cast<uint32_t>(c[u]) * pitch);
   }
@@ -261,7 +261,7 @@ struct PackedRowLoader {
     uint32_t slot[N], mw[N], pre[N];
     u32x3 raw[N];
   };
-  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N]) const {
+  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N], const float (&)[N]) const {
 #pragma unroll
     for (int u = 0; u < N; ++u) {
       b.slot[u] = static_cast<uint32_t>(c[u]) * static_cast<uint32_t>(S);
@@ -309,7 +309,7 @@ __device__ __forceinline__ void gather_batch_with(const L& ld, const int32_t* __
     c[u] = colind[e + u];
     v[u] = val[e + u];
   }
-  ld.request(b, c);
+  ld.request(b, c, v);
   ld.follow(b);
   ld.apply(b, v, acc);
 }
@@ -337,7 +337,7 @@ __device__ __forceinline__ float4 walk_row(const L& ld, const int32_t* __restric
       c0[u] = ci[u];
       v0[u] = va[u];
     }
-    ld.request(ba, c0);
+    ld.request(ba, c0, v0);
     for (;;) {
       i += UNROLL;
       const bool more_a = i + UNROLL <= len;
@@ -349,10 +349,10 @@ __device__ __forceinline__ float4 walk_row(const L& ld, const int32_t* __restric
         }
       }
       ld.follow(ba);
-      if (L::kAhead && more_a) ld.request(bb, c1);
+      if (L::kAhead && more_a) ld.request(bb, c1, v1);
       ld.apply(ba, v0, acc);
       if (!more_a) break;
-      if (!L::kAhead) ld.request(bb, c1);
+      if (!L::kAhead) ld.request(bb, c1, v1);
       i += UNROLL;
       const bool more_b = i + UNROLL <= len;
       if (more_b) {
@@ -363,10 +363,10 @@ __device__ __forceinline__ float4 walk_row(const L& ld, const int32_t* __restric
         }
       }
       ld.follow(bb);
-      if (L::kAhead && more_b) ld.request(ba, c0);
+      if (L::kAhead && more_b) ld.request(ba, c0, v0);
       ld.apply(bb, v1, acc);
       if (!more_b) break;
-      if (!L::kAhead) ld.request(ba, c0);
+      if (!L::kAhead) ld.request(ba, c0, v0);
     }
   }
   if (i + 4 <= len) { gather_batch_with<4>(ld, ci, va, i, acc); i += 4; }
@@ -422,6 +422,103 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_spmm_row_packed(
     ld.voff = lane * 8;
     ld.pitch = pitch;
     acc = walk_row<UNROLL>(ld, ci, va, len);
+  }
+  store4<uint16_t>(y + row * ldy + lane * 4, acc);
+}
+
+// ---- wave per row, gathering 12-bit CODED operand rows (bf16, d = 256) ----------------------------------------------------
+// The dense operands of a step (relu(BatchNorm) + x0, three quarters non-zero; the backward's gradients) have no zeros to
+// elide, but the exponents of one bf16 row span few binades: spmm_coded.hip writes every row as sign + 4-bit exponent + 7-bit
+// mantissa, 256 x 12 bits = 384 bytes = 3 of the 4 fetch lines of a dense row, and folds the row's scale 2^(E - 15) into a
+// per-launch copy `vc` of the CSR values (format and the argument for bit equality: the head of that file).  What the packed
+// kernel above taught decides the shape of this one: NO per-row metadata on the gather path (the scale reaches the wave
+// through the scalar load that fetches the value anyway) and ONE round trip per entry (lane l reads dword l and half l of the
+// slot, fixed offsets, nothing depends on another load; kAhead stays false).  An entry whose value carries the sign bit is
+// an escape: the wave reads the dense row of x instead and multiplies by |v|, the original value — a wave-uniform branch
+// per entry, so batches mix both kinds.  The FMAs are k_spmm_row's in k_spmm_row's order.  *n_unsupported != 0 (a stored
+// value with the sign bit set: the tag would be ambiguous) runs the whole launch on the dense rows and the original values.
+struct CodedRowLoader {
+  static constexpr bool kAhead = false;
+  __amdgpu_buffer_rsrc_t rc, rx;    // the slots, the dense rows
+  int voff_w, voff_h, voff_x;       // this lane's dword and the dword of its half in a slot; its 8 bytes of a dense row
+  uint32_t sel;                     // v_perm selector: the lane's half as bytes {b3, b3, b2, b2}
+  uint32_t pitch;
+  template <int N> struct Batch { uint32_t w[N], h[N]; };
+  static __device__ __forceinline__ bool escaped(float v) { return (__float_as_uint(v) >> 31) != 0u; }   // wave-uniform
+  template <int N> __device__ __forceinline__ void request(Batch<N>& b, const int32_t (&c)[N], const float (&v)[N]) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      if (escaped(v[u])) {
+        const u32x2 r = BufRow<uint16_t>::load(rx, voff_x, static_cast<uint32_t>(c[u]) * pitch);
+        b.w[u] = r.x;
+        b.h[u] = r.y;
+      } else {
+        const uint32_t slot = static_cast<uint32_t>(c[u]) * static_cast<uint32_t>(kCodedSlot);
+        b.w[u] = __builtin_amdgcn_raw_buffer_load_b32(rc, voff_w, static_cast<int>(slot), 0);
+        b.h[u] = __builtin_amdgcn_raw_buffer_load_b32(rc, voff_h, static_cast<int>(slot), 0);
+      }
+    }
+  }
+  template <int N> __device__ __forceinline__ void follow(Batch<N>&) const {}
+  template <int N> __device__ __forceinline__ void apply(const Batch<N>& b, const float (&v)[N], float4& acc) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      float4 f;
+      if (escaped(v[u])) {
+        u32x2 r;
+        r.x = b.w[u];
+        r.y = b.h[u];
+        f = BufRow<uint16_t>::widen(r);
+      } else {
+        const uint32_t w = b.w[u];
+        const uint32_t z = ((w >> 4) & 0x07800780u) | (__builtin_amdgcn_perm(0u, b.h[u], sel) & 0x807f807fu);
+        f.x = __uint_as_float((w << 16) & 0x87ff0000u);
+        f.y = __uint_as_float(w & 0x87ff0000u);
+        f.z = __uint_as_float(z << 16);
+        f.w = __uint_as_float(z & 0xffff0000u);
+      }
+      fma4(acc, __uint_as_float(__float_as_uint(v[u]) & 0x7fffffffu), f);
+    }
+  }
+};
+
+template <int UNROLL>
+__global__ __launch_bounds__(kWavesPerBlock * 64) void k_spmm_row_coded(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ colind, const float* __restrict__ val,
+    const float* __restrict__ val_coded, const uint16_t* __restrict__ x, uint32_t pitch, uint32_t x_bytes,
+    const void* __restrict__ coded, uint32_t coded_bytes, const int32_t* __restrict__ n_unsupported,
+    uint16_t* __restrict__ y, int64_t ldy, int64_t n_rows, LongQueue lq) {
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t row = blk * kWavesPerBlock + wid;  // wave-uniform
+  if (row >= n_rows) return;
+  const int64_t e0 = rowptr[row];
+  const int64_t e1 = rowptr[row + 1];
+  if (e1 - e0 > lq.long_len) {   // wave-uniform
+    push_long_row(lq, row, e1 - e0, lane, 64);
+    return;
+  }
+  const int32_t* __restrict__ ci = colind + e0;
+  const int len = static_cast<int>(e1 - e0);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), 0, x_bytes, 0x00020000);
+  float4 acc;
+  if (*n_unsupported == 0) {     // wave-uniform: a scalar load
+    CodedRowLoader ld;
+    ld.rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(coded), 0, coded_bytes, 0x00020000);
+    ld.rx = rx;
+    ld.voff_w = lane * 4;
+    ld.voff_h = 256 + (lane >> 1) * 4;
+    ld.voff_x = lane * 8;
+    ld.sel = (lane & 1) ? 0x03030202u : 0x01010000u;
+    ld.pitch = pitch;
+    acc = walk_row<UNROLL>(ld, ci, val_coded + e0, len);
+  } else {
+    DenseRowLoader ld;
+    ld.rsrc = rx;
+    ld.voff = lane * 8;
+    ld.pitch = pitch;
+    acc = walk_row<UNROLL>(ld, ci, val + e0, len);
   }
   store4<uint16_t>(y + row * ldy + lane * 4, acc);
 }
@@ -1471,10 +1568,26 @@ bool packed_rule(const Choice& c, int32_t d, size_t elem_size, int64_t n_cols, i
          static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(slot_bytes) + kPackedTail < (static_cast<uint64_t>(1) << 32);
 }
 
+// The coded copy of the operand of one launch (sgf_spmm_coded; spmm_coded.hip writes it): 384-byte slots, the CSR values
+// with the rows' scales folded in, and the device count of stored values the tag cannot mark.  The one rule for when the
+// launch gathers it — shared by launch and sgf_spmm_coded_supported: SGF_SPMM_CODED != 0, bf16 rows of exactly 256 columns,
+// the launch would run k_spmm_row, slots within 32-bit offsets.  (Rows handed to the long-row queue are reduced from the
+// dense rows and the original values.)
+EnvInt g_coded{"SGF_SPMM_CODED", 1};
+struct CodedOperand {
+  const void* slots;
+  const float* val_coded;
+  const int32_t* n_unsupported;
+};
+bool coded_rule(const Choice& c, int32_t d, size_t elem_size, int64_t n_cols) {
+  return g_coded.get() != 0 && c.arm == Arm::Row && elem_size == 2 && d == 256 &&
+         static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(kCodedSlot) < (static_cast<uint64_t>(1) << 32);
+}
+
 template <typename T>
 int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const T* x, int64_t ldx, int64_t n_cols,
            T* y, int64_t ldy, int64_t n_rows, int32_t d, hipStream_t st, const LongQueue& lq,
-           float* partial, bool stream, const PackedOperand* pk = nullptr) {
+           float* partial, bool stream, const PackedOperand* pk = nullptr, const CodedOperand* cd = nullptr) {
   constexpr int UNROLL = 8;
   const dim3 block(kWavesPerBlock * 64);
   uint64_t x_bytes;
@@ -1514,6 +1627,13 @@ int launch(const int64_t* rowptr, const int32_t* colind, const float* val, const
         if (pk->slot_bytes == 384) SGF_ROWP(384);
         else SGF_ROWP(448);
 #undef SGF_ROWP
+        break;
+      }
+      if (cd && coded_rule(c, d, sizeof(T), n_cols)) {
+        hipLaunchKernelGGL((k_spmm_row_coded<UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st, rowptr, colind, val,
+                           cd->val_coded, reinterpret_cast<const uint16_t*>(x), static_cast<uint32_t>(ldx * sizeof(T)),
+                           static_cast<uint32_t>(x_bytes), cd->slots, static_cast<uint32_t>(n_cols * kCodedSlot),
+                           cd->n_unsupported, reinterpret_cast<uint16_t*>(y), ldy, n_rows, lq);
         break;
       }
       hipLaunchKernelGGL((k_spmm_row<T, UNROLL>), dim3(static_cast<unsigned>(nb)), block, 0, st, rowptr, colind,
@@ -1584,7 +1704,8 @@ int check_spmm_operands(const char* fn, const void* x, int64_t ldx, const void* 
 
 int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, const void* x, int64_t ldx,
                 int64_t n_cols, void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, const LongQueue& lq,
-                float* partial, hipStream_t st, const char* fn, bool stream = false, const PackedOperand* pk = nullptr) {
+                float* partial, hipStream_t st, const char* fn, bool stream = false, const PackedOperand* pk = nullptr,
+                const CodedOperand* cd = nullptr) {
   SGF_REQUIRE(n_rows >= 0 && d >= 0 && n_cols >= 0, SGF_E_INVALID, "%s: negative size", fn);
   if (n_rows == 0 || d == 0) return SGF_OK;
   SGF_REQUIRE(rowptr && x && y, SGF_E_INVALID, "%s: null pointer", fn);
@@ -1595,7 +1716,7 @@ int spmm_common(const int64_t* rowptr, const int32_t* colind, const float* val, 
     return launch<float>(rowptr, colind, val, static_cast<const float*>(x), ldx, n_cols, static_cast<float*>(y), ldy,
                          n_rows, d, st, lq, partial, stream);
   return launch<uint16_t>(rowptr, colind, val, static_cast<const uint16_t*>(x), ldx, n_cols,
-                          static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream, pk);
+                          static_cast<uint16_t*>(y), ldy, n_rows, d, st, lq, partial, stream, pk, cd);
 }
 }  // namespace
 
@@ -1690,6 +1811,33 @@ extern "C" int sgf_spmm_packed(const int64_t* rowptr, const int32_t* colind, con
   if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
   const PackedOperand pk{packed, slot_bytes, overflow};
   return spmm_common(rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype, lq, partial, st, fn, false, &pk);
+}
+
+// sgf_spmm_split with a 12-bit coded copy of x and the scaled CSR values next to the dense ones (spmm_coded.hip:
+// sgf_spmm_code_rows, sgf_spmm_code_values).  The launch gathers the slots when coded_rule holds and no stored value is
+// negative (read on the device); anything else runs sgf_spmm_split's kernels on the dense rows, and so do the rows longer
+// than long_len in every case.  Results are those of sgf_spmm_split bit for bit either way.
+extern "C" int32_t sgf_spmm_coded_supported(int32_t d, int32_t dtype, int64_t ldx, int64_t ldy, int64_t n_cols,
+                                            int32_t aligned16) {
+  if (dtype != SGF_F32 && dtype != SGF_BF16) return 0;
+  const size_t esz = dtype == SGF_BF16 ? 2 : 4;
+  const Choice c = choose_for_operands(d, esz, ldx, ldy, n_cols, aligned16 != 0, false);
+  return coded_rule(c, d, esz, n_cols) ? 1 : 0;
+}
+
+extern "C" int sgf_spmm_coded(const int64_t* rowptr, const int32_t* colind, const float* val, const float* val_coded,
+                              const void* x, int64_t ldx, int64_t n_cols, const void* coded, const int32_t* n_unsupported,
+                              void* y, int64_t ldy, int64_t n_rows, int32_t d, int32_t dtype, int64_t long_len,
+                              int64_t long_segments, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "sgf_spmm_coded";
+  SGF_REQUIRE(coded && val_coded && n_unsupported, SGF_E_INVALID, "%s: null pointer", fn);
+  SGF_REQUIRE(reinterpret_cast<uintptr_t>(coded) % 128 == 0, SGF_E_INVALID, "%s: the coded buffer must be 128-byte aligned", fn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LongQueue lq;
+  float* partial;
+  if (const int rc = spmm_long_queue(fn, long_len, long_segments, d, workspace, workspace_bytes, st, &lq, &partial)) return rc;
+  const CodedOperand cd{coded, val_coded, n_unsupported};
+  return spmm_common(rowptr, colind, val, x, ldx, n_cols, y, ldy, n_rows, d, dtype, lq, partial, st, fn, false, nullptr, &cd);
 }
 
 // sgf_spmm_split for a CSR whose gathers mostly hit in L2 (a locality-restoring node order, sgf_reorder): bf16 rows

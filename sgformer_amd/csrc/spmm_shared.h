@@ -56,6 +56,11 @@ static __device__ __forceinline__ void push_long_row(const LongQueue& q, int64_t
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// The 12-bit coded copy of a bf16 [n, 256] operand (spmm_coded.hip writes it, spmm.hip: k_spmm_row_coded gathers it): bytes
+// per row, and the scale byte of a row that is not coded (a coded row's is its largest exponent field, 1..254).
+constexpr int kCodedSlot = 384;
+constexpr uint8_t kCodedEscaped = 255;
+
 // The long-row workspace (sgf_spmm_split_workspace_bytes): the queue's counter, its entries, one fp32 partial row of d
 // values per segment — each part 256-byte aligned.
 constexpr size_t kLongCountOff = 0, kLongEntriesOff = 256;

@@ -11,12 +11,13 @@ from typing import Optional
 import torch
 
 from . import _lib
+from . import coded as _coded
 from .kernels import HipKernels, LONG_ROW, _SEGMENT
 
 _F32 = torch.float32
 
 
-K = HipKernels()
+K = _coded.install(HipKernels())
 
 
 def _has(table, name: str, *args) -> bool:
@@ -507,21 +508,22 @@ def _own_block_spmm(graph, plan, own, x, n_local: int, transposed: bool):
 
 class _SpMM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, graph, shard, packed=None):
+    def forward(ctx, x, graph, shard, packed=None, layer=None):
         K.check(x)
-        ctx.graph, ctx.shard = graph, shard
+        ctx.graph, ctx.shard, ctx.layer = graph, shard, layer
         if shard is not None:
             # node-sharded: rows of A local, X rows gathered from all ranks (halo all-gather)
             return _sharded_spmm(graph, x, shard, False)
-        return spmm_on(graph, x, False, packed=packed)
+        return spmm_on(graph, x, False, packed=packed, coded_class=None if layer is None else f"fwd{layer}")
 
     @staticmethod
     def backward(ctx, gy):
         graph, shard = ctx.graph, ctx.shard
         if shard is not None:
             # dX_local = (A^T dY)[local rows]: local rows of the CSR of A^T times the sharded dY
-            return _sharded_spmm(graph, gy.contiguous(), shard, True), None, None, None
-        return spmm_on(graph, gy.contiguous(), True), None, None, None
+            return _sharded_spmm(graph, gy.contiguous(), shard, True), None, None, None, None
+        coded_class = None if ctx.layer is None else f"bwd{ctx.layer}"
+        return spmm_on(graph, gy.contiguous(), True, coded_class=coded_class), None, None, None, None
 
 
 def spmm_packed_slot(graph, x_shape, dtype, slot_bytes: int) -> int:
@@ -533,11 +535,40 @@ def spmm_packed_slot(graph, x_shape, dtype, slot_bytes: int) -> int:
     return slot_bytes if K.spmm_packed_supported(x_shape, dtype, slot_bytes) else 0
 
 
-def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None) -> torch.Tensor:
+# The plain wave-per-row launches of a full-graph training step may gather a lossless 12-bit coded copy of their operand
+# (csrc/spmm_coded.hip, k_spmm_row_coded: 384 bytes per row where the dense row takes 512; SGF_SPMM_CODED=0 turns it off).
+# Each such launch first writes the coded rows and a copy of the CSR values with the rows' scales folded in (two streaming
+# passes, 0.94 + 0.5 GB of scratch at products size, released after the launch), so it is used only where the gather saves
+# more than they cost: CODED_CLASSES names the launch classes — "fwd2", "fwd3" (the forward SpMMs of GCN layers 2 and 3;
+# layer 1 gathers its packed copy), "bwd3", "bwd2", "bwd1" — set from the step A/B of profiles/spmm_coded_ab.txt: added one at
+# a time only "fwd2" lowers the step by more than three times the spread of its runs; the other four each gain 0.9-1.6 ms
+# there, under the bound, and stay off until an A/B resolves them.
+# Operands of fewer than CODED_MIN_NODES rows stay dense (mini-batches: the passes are launch-bound there).
+CODED_MIN_NODES = 65536
+CODED_CLASSES = frozenset({"fwd2"})
+
+
+def _coded_ok(graph, x: torch.Tensor, out, packed, coded_class) -> bool:
+    return (coded_class in CODED_CLASSES and packed is None and out is None and x.dim() == 2 and x.shape[1] == 256
+            and x.dtype == torch.bfloat16 and x.shape[0] >= CODED_MIN_NODES and x.is_contiguous()
+            and _has(K, "spmm_coded") and not torch.cuda.is_current_stream_capturing()
+            and K.spmm_coded_supported(x.shape, x.dtype))
+
+
+def _spmm_coded(coded_class, rp, ci, va, x: torch.Tensor, n: int, segs: int) -> torch.Tensor:
+    slots, scale, n_escaped = K.spmm_code_rows(x)
+    if _coded.escape_log is not None:
+        _coded.escape_log.append((coded_class, n_escaped, x.shape[0]))
+    val_coded, n_unsupported = K.spmm_code_values(ci, va, scale)
+    return K.spmm_coded(rp, ci, va, val_coded, x, slots, n_unsupported, n, long_segments=segs)
+
+
+def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None, coded_class=None) -> torch.Tensor:
     """A x or A^T x on one GPU, on the first kernel that applies: the LDS-staged row-block kernel (graph.blocked, rows of at most
     256 columns); matrix-core tiles + gather remainder (graph.tiled and _tile_operand_ok); the stream kernel (graph.locality);
     the wave-per-row launch gathering `packed`, the producer's packed copy of x (K.bn_apply_packed; A x into a fresh tensor
-    only); else the wave-per-row kernel on x, long rows split over workgroups."""
+    only); the wave-per-row launch gathering a 12-bit coded copy of x made here (`coded_class` in CODED_CLASSES, _coded_ok);
+    else the wave-per-row kernel on x, long rows split over workgroups."""
     rp, ci, va, segs = graph.arrays(transposed)
     plan = graph.plan(x.dtype, transposed) if (graph.blocked and x.shape[1] <= 256) else None
     if plan is not None:
@@ -553,10 +584,13 @@ def spmm_on(graph, x: torch.Tensor, transposed: bool, out=None, packed=None) -> 
         return K.spmm(rp, ci, va, x, graph.n, out=out, long_segments=segs, stream_hint=True)
     if packed is not None and not transposed and out is None:
         return K.spmm_packed(rp, ci, va, x, packed, graph.n, long_segments=segs)
+    if _coded_ok(graph, x, out, packed, coded_class):
+        return _spmm_coded(coded_class, rp, ci, va, x, graph.n, segs)
     return K.spmm(rp, ci, va, x, graph.n, out=out, long_segments=segs)
 
 
-def spmm(graph, x: torch.Tensor, shard=None, packed=None) -> torch.Tensor:
+def spmm(graph, x: torch.Tensor, shard=None, packed=None, layer=None) -> torch.Tensor:
     """Y = A X with A the cached normalised adjacency (torch_sparse.matmul(adj, x) in the reference).  `packed`: a packed
-    copy of X for the forward gathers (spmm_packed_slot says when one is of use); the backward never reads it."""
-    return _SpMM.apply(x, graph, shard, packed)
+    copy of X for the forward gathers (spmm_packed_slot says when one is of use); the backward never reads it.  `layer`:
+    the 1-based GCN layer of this product, which names its forward and backward launch classes (CODED_CLASSES)."""
+    return _SpMM.apply(x, graph, shard, packed, layer)

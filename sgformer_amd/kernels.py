@@ -20,7 +20,7 @@ LONG_ROW = 1024
 _SEGMENT = 1024   # = sgf_spmm_segment_len()
 
 # launches by entry, for the tests that have to see which path a step took
-counters = {"spmm_packed": 0}
+counters = {"spmm_packed": 0, "spmm_coded": 0}
 
 
 class PackedRows:

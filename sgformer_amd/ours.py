@@ -64,7 +64,9 @@ OVERLAP_MIN_NODES = 65536
 # reads x0 = relu(BatchNorm(stem)): 119-128 non-zeros of 256 per row (sd 8, maximum 160) on the products recipe, so the
 # 176 values of a 384-byte slot lie 6 sd above the mean.  Layers 2 and 3 read relu(BatchNorm(z)) + x0: 190-195 non-zeros
 # (sd 7, maximum 227) against the 208 of a 448-byte slot, 2 sd, and 0.1-3 % of the rows overflow — one such row sends the
-# whole launch to the dense rows, so they stay dense (profiles/spmm_packed_zero_fractions.md).
+# whole launch to the dense rows, so they get no packed copy (profiles/spmm_packed_zero_fractions.md); those launches and the
+# backward ones can gather a lossless 12-bit coded copy instead (ops.CODED_CLASSES in sgformer_amd/graph.py names the ones
+# that do: layer 2's forward as merged).
 PACKED_SLOT_BYTES = (384, 0, 0)
 _side_streams = {}
 
@@ -233,9 +235,10 @@ class GraphConvLayer(nn.Module):
     def reset_parameters(self):
         self.W.reset_parameters()
 
-    def propagate(self, x, edge_index, packed=None):
+    def propagate(self, x, edge_index, packed=None, layer=None):
         """A_norm x (large/ours.py:26-34): the cached CSR of `edge_index` times x.  `packed` (not in the reference
-        signature): the packed copy of x its producer wrote (GraphConv.pack_request), gathered instead of x."""
+        signature): the packed copy of x its producer wrote (GraphConv.pack_request), gathered instead of x.  `layer`
+        (neither): the 1-based position of this layer, the launch class of its SpMMs (ops.spmm)."""
         shard = self._shard
         if isinstance(edge_index, ops.CSRGraph):   # SGFormer.forward resolved (and maybe re-ordered) it already
             graph = edge_index
@@ -246,7 +249,7 @@ class GraphConvLayer(nn.Module):
             # subgraph, no halo; only the attention / BatchNorm partial sums cross ranks
             graph = ops.graph_cache.get(edge_index, x.shape[0])
         shard = None if (shard is not None and shard.local_graph) else shard
-        return ops.spmm(graph, x, shard, packed if shard is None else None)
+        return ops.spmm(graph, x, shard, packed if shard is None else None, layer)
 
     def forward(self, x, edge_index, x0, bn_stats=False):
         """`bn_stats` (not in the reference signature): also return the batch statistics (mean, var, count) of
@@ -384,7 +387,7 @@ class GraphConv(nn.Module):
                 x = x_first
             for i, conv in enumerate(self.convs):
                 bn = self.bns[i + 1]
-                y = conv.propagate(x, edge_index, packed)
+                y = conv.propagate(x, edge_index, packed, i + 1)
                 packed = None
                 # this layer's BatchNorm pass writes the next SpMM's operand: packed too, if that launch gathers it
                 req = self.pack_request(i + 1, x0.shape[0], x0.dtype, edge_index) if self.use_act else None
